@@ -6,11 +6,15 @@ One step = dirt rasterise forward + registered backward over one synthetic frame
 (SURVEY 8d distribution, seed = rank), inputs resident in HBM.  N>1: one process per GPU, frames
 sharded across ranks with no data-path collective (weak scaling); value = all ranks' pixels / max time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  Extra keys: roofline (dominant kernel, HIP-event timed), cpu_baseline
-(the CPU oracle on the box's host cores, rank 0 at N=1), kernels (per-kernel average microseconds).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(metric, value, ms_per_step, config).  --dump-outputs DIR also writes the last timed step's outputs as .npy.
+--full adds everything else, each measured in runs of its own after the timed steps: roofline (dominant
+kernel, HIP-event timed), kernels_us (per-kernel average microseconds), legs (the public op, the recompute
+backward, cold cache, batched, deep scene, and at N > 1 the collectives), cpu_baseline and parity_vs_oracle
+(the CPU oracle on the host cores, rank 0 at N=1), r5_clip_stats.
 """
 import argparse
 import json
@@ -193,12 +197,40 @@ def timed(run, n_calls, barrier, world, device, shared):
     return elapsed
 
 
+DUMP_BUDGET_BYTES = 63 * 10**6  # all files of one --dump-outputs together stay under 64 MB, headers included
+DUMP_SAMPLE_SEED = 20_000
+
+
+def dump_outputs(dirname, sess):
+    """Write what the step's caller receives -- forward: pixels; backward: grad_background, grad_vertices,
+    grad_vertex_colors -- from the session's buffers as dirname/<name>.npy (float32).  Whole arrays while they
+    fit DUMP_BUDGET_BYTES together (config 3: 29 MB); otherwise each array's share of the budget, as a 1-D
+    array of the elements at fixed flat indices (sorted, drawn without replacement from DUMP_SAMPLE_SEED and
+    the array's size, so the same for every run and build).  The caller has synchronised the device."""
+    arrays = [(name, getattr(sess, name).detach().cpu().numpy().astype(np.float32, copy=False))
+              for name in ("pixels", "grad_background", "grad_vertices", "grad_vertex_colors")]
+    total = sum(a.nbytes for _, a in arrays)
+    os.makedirs(dirname, exist_ok=True)
+    for k, (name, a) in enumerate(arrays):
+        if total > DUMP_BUDGET_BYTES:
+            n = max(1, int(a.size * DUMP_BUDGET_BYTES / total))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED + k).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (pixels and the three gradients, "
+                         "rank 0's frames) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, per-kernel times, the extra legs, the CPU "
+                         "baseline and the parity with the oracle (the options below choose among them)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
     ap.add_argument("--graph-steps", type=int, default=200,
                     help="steps captured per HIP graph (each replay runs that many complete steps; default: all "
@@ -216,6 +248,8 @@ def main():
                     help="after the warmup steps, keep running the step untimed for this long (GPU clock ramp); "
                          "0 = off")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -285,7 +319,30 @@ def main():
     elapsed = timed(timed_loop, 1, barrier, world, device, shared)
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * B * H * W * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sess)  # (the session's buffers hold the last timed step's results)
+    headline = {
+        "metric": "Mpixels/s fwd+bwd @1024^2 50k-tri",
+        "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "clock_warm": clock_warm, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%s: %d frame(s)/rank x %d random tris (r=%gpx), %dx%dx%d, fwd+bwd" %
+                               (args.config, B, F, _r, H, W, C),
+                   "frames_per_rank": B, "height": H, "width": W, "channels": C, "faces": F, "vertices": V,
+                   "parallelism": "frames sharded over %d rank(s); no collective in the step (the output "
+                                  "gather is measured as its own leg, legs.gather, under --full)" % world,
+                   "hip_graph": not args.no_graph, "steps_per_graph": gs},
+    }
+    if not args.full:
+        # a plain run ends here: the headline alone
+        if rank == 0:
+            print(json.dumps(headline))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
+    # ---- everything below: --full only
     # per-kernel HIP-event timing (same kernels, eager launches, outside the timed loop)
     def kernel_times(fn, n):
         _lib.profile_enable(True)
@@ -782,25 +839,15 @@ def main():
         par = parity(sess, ref)
 
     if rank == 0:
-        out = {
-            "metric": "Mpixels/s fwd+bwd @1024^2 50k-tri",
-            "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "clock_warm": clock_warm, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s: %d frame(s)/rank x %d random tris (r=%gpx), %dx%dx%d, fwd+bwd" %
-                                   (args.config, B, F, _r, H, W, C),
-                       "frames_per_rank": B, "height": H, "width": W, "channels": C, "faces": F, "vertices": V,
-                       "parallelism": "frames sharded over %d rank(s); no collective in the step (the output "
-                                      "gather is measured as its own leg, legs.gather)" % world,
-                       "hip_graph": not args.no_graph, "steps_per_graph": gs},
+        out = dict(headline)
+        out.update({
             "roofline": roofline,
             "cpu_baseline": cpu,
             "parity_vs_oracle": par,
             "r5_clip_stats": clip_stats,
             "kernels_us": {k: round(u, 2) for k, u in kern_us.items()},
             "legs": legs,
-        }
+        })
         print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()

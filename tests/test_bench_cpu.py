@@ -31,6 +31,40 @@ def test_configs_and_host_info():
     assert bench.cpu_threads() >= 1
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: whole float32 arrays while they fit the budget; past it a fixed, seeded sample of every
+    array (the same elements on every call) whose files stay within the budget together."""
+    import os
+    import types
+
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(0)
+    sess = types.SimpleNamespace(pixels=torch.randn(2, 5, 7, 3, generator=g),
+                                 grad_background=torch.randn(2, 5, 7, 3, generator=g),
+                                 grad_vertices=torch.randn(2, 9, 4, generator=g),
+                                 grad_vertex_colors=torch.randn(2, 9, 3, generator=g))
+    names = ("pixels", "grad_background", "grad_vertices", "grad_vertex_colors")
+    bench.dump_outputs(str(tmp_path / "whole"), sess)
+    assert sorted(os.listdir(tmp_path / "whole")) == sorted(n + ".npy" for n in names)
+    for n in names:
+        a = np.load(tmp_path / "whole" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, getattr(sess, n).numpy())
+    total = sum(getattr(sess, n).numel() * 4 for n in names)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", total // 3)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), sess)
+    n_bytes = 0
+    for n in names:
+        a, b = (np.load(tmp_path / d / (n + ".npy")) for d in ("s1", "s2"))
+        full = getattr(sess, n).numpy().reshape(-1)
+        assert a.dtype == np.float32 and a.ndim == 1 and 1 <= a.size < full.size
+        assert np.array_equal(a, b) and np.isin(a, full).all()
+        n_bytes += a.nbytes
+    assert n_bytes <= total // 3
+
+
 def test_cpu_share_evidence():
     """The CPU baseline records where its thread count comes from (SURVEY 8d asks for all host cores; the pool
     grants one GPU's job a share, OMP_NUM_THREADS on the box): cgroup quota / cpuset when readable."""

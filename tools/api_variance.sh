@@ -2,9 +2,9 @@
 # The public op's eager leg across repeated bench runs on one box: the driver's command twice, the default
 # (200-step) command, the driver's command again.   tools/api_variance.sh
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/apix; mkdir -p $O; cd $R
-for k in d1 d2; do timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/$k.json 2>$O/$k.err || exit 1; done
-timeout -k 10 300 python3 bench.py --no-cpu-baseline > $O/full.json 2>$O/full.err || exit 1
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/d3.json 2>$O/d3.err || exit 1
+for k in d1 d2; do timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/$k.json 2>$O/$k.err || exit 1; done
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline > $O/full.json 2>$O/full.err || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/d3.json 2>$O/d3.err || exit 1
 python3 - <<'PY'
 import json, os
 O = os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out", "apix")
