@@ -16,6 +16,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <cstring>
 
 #include <list>
 #include <map>
@@ -178,25 +179,30 @@ struct ScratchCache {
 // (or views of the same storage, same elements), unmodified since (version counters unchanged: every in-place op on
 // them or a view bumps it), at the same B, H, W, F, takes dirt_rasterise_fwd_resolve: no setup, bins or visibility
 // pass, pixels bit-identical.  Its backward reads the shared saved records (read-only) and its own g-buffer copy.
-// Writes that bypass the version counter (`.data`, raw pointers) are not seen -- the same limitation as autograd's
-// own saved-tensor checks; DIRT_SHARE_GEOMETRY=0 turns the cache off.  A capture's entries are its own (its g-buffer
-// is recomputed by its replays), and eager entries are never used inside a capture or the other way round.
+// OPT-IN (DIRT_SHARE_GEOMETRY=1 or set_geometry_sharing(true); off by default): writes that bypass the version counter
+// (`.data`, a DLPack alias, raw pointers) are not seen -- the same limitation as autograd's own saved-tensor checks --
+// so a caller who opts in promises to change the geometry only through ops that bump it.  Inference tensors have no
+// version counter: they are never stored and never hit.  The entry also records the version of the g-buffer it
+// holds (the tensor the first forward returned to its caller): an in-place edit of it makes the next render a full
+// one.  A capture's entries are its own (its g-buffer is recomputed by its replays), and eager entries are never used
+// inside a capture or the other way round.
 struct GeomCache {
     struct Entry {
         int dev = -1;
         uintptr_t stream = 0;
         unsigned long long cid = 0;
         at::Tensor v, f, gbuffer, saved;
-        int64_t vver = 0, fver = 0, H = 0, W = 0;
+        int64_t vver = 0, fver = 0, gver = 0, H = 0, W = 0;
     };
     std::mutex mu;
     std::list<Entry> entries;  // one per (device, stream, capture id), a few at most
-    // on unless DIRT_SHARE_GEOMETRY=0; set_geometry_sharing() switches it at run time (both implementations)
+    // off unless DIRT_SHARE_GEOMETRY is set (to anything but 0); set_geometry_sharing() switches it at run time (both
+    // implementations)
     static std::atomic<int> &flag()
     {
         static std::atomic<int> v{[] {
             const char *e = getenv("DIRT_SHARE_GEOMETRY");
-            return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : 1;
+            return (e && *e && strcmp(e, "0") != 0) ? 1 : 0;
         }()};
         return v;
     }
@@ -216,10 +222,12 @@ struct GeomCache {
     std::pair<at::Tensor, at::Tensor> find(int dev, hipStream_t stream, unsigned long long cid, const at::Tensor &v,
                                            const at::Tensor &f, int64_t H, int64_t W)
     {
+        if (v.is_inference() || f.is_inference()) return {at::Tensor(), at::Tensor()};  // (no version counter)
         std::lock_guard<std::mutex> g(mu);
         for (const Entry &e : entries)
             if (e.dev == dev && e.stream == reinterpret_cast<uintptr_t>(stream) && e.cid == cid && e.H == H && e.W == W &&
-                same(e.v, v) && same(e.f, f) && e.vver == (int64_t)v._version() && e.fver == (int64_t)f._version())
+                same(e.v, v) && same(e.f, f) && e.vver == (int64_t)v._version() && e.fver == (int64_t)f._version() &&
+                e.gver == (int64_t)e.gbuffer._version())
                 return {e.gbuffer, e.saved};
         return {at::Tensor(), at::Tensor()};
     }
@@ -230,6 +238,8 @@ struct GeomCache {
         entries.remove_if([&](const Entry &e) {
             return e.dev == dev && e.stream == reinterpret_cast<uintptr_t>(stream) && e.cid == cid;
         });
+        // (inference tensors -- made under torch.inference_mode() -- track no version: never shared)
+        if (v.is_inference() || f.is_inference() || gbuffer.is_inference()) return;
         Entry e;
         e.dev = dev;
         e.stream = reinterpret_cast<uintptr_t>(stream);
@@ -238,6 +248,7 @@ struct GeomCache {
         e.f = f.detach();
         e.vver = (int64_t)v._version();
         e.fver = (int64_t)f._version();
+        e.gver = (int64_t)gbuffer._version();
         e.H = H;
         e.W = W;
         e.gbuffer = gbuffer;

@@ -167,10 +167,14 @@ class _GeomCache:
     remembers its geometry -- vertices' and faces' storage, offset, shape, strides and version counters, as detached
     aliases -- with its g-buffer and saved records; a forward on the same, unmodified tensors (or views of the same
     elements) at the same frame size takes dirt_rasterise_fwd_resolve (the resolve alone, pixels bit-identical).
-    Writes that bypass the version counter (`.data`, raw pointers) are not seen, like autograd's own saved-tensor
-    checks; DIRT_SHARE_GEOMETRY=0 turns it off."""
+    OPT-IN: off unless DIRT_SHARE_GEOMETRY=1 is set, `set_geometry_sharing(True)` is called or the render runs inside
+    `shared_geometry()`.  Writes that bypass the version counter (`.data`, a DLPack alias, raw pointers) are not seen,
+    like autograd's own saved-tensor checks: a caller who opts in changes the geometry only through ops that bump it.
+    Inference tensors (made under torch.inference_mode()) have no version counter: they are never stored and never
+    hit.  The entry records the version of the g-buffer it holds (the tensor the first forward returned), so an
+    in-place edit of that tensor makes the next render a full one."""
 
-    enabled = os.environ.get("DIRT_SHARE_GEOMETRY", "1") not in ("", "0")
+    enabled = os.environ.get("DIRT_SHARE_GEOMETRY", "") not in ("", "0")
 
     def __init__(self):
         self._lock = threading.Lock()
@@ -183,17 +187,24 @@ class _GeomCache:
                 tuple(s if n > 1 else 0 for s, n in zip(t.stride(), t.shape)), t.dtype, t._version)
 
     def find(self, key, vertices, faces, H, W):
+        if vertices.is_inference() or faces.is_inference():
+            return None
         with self._lock:
             e = self._d.get(key)
-        if e is None or e[0] != (self._ident(vertices), self._ident(faces), H, W):
+        if (e is None or e[0] != (self._ident(vertices), self._ident(faces), H, W)
+                or e[4] != e[2]._version):
             return None
         return e[2], e[3]
 
     def store(self, key, vertices, faces, H, W, gbuffer, saved):
+        if vertices.is_inference() or faces.is_inference() or gbuffer.is_inference():
+            with self._lock:
+                self._d.pop(key, None)
+            return
         with self._lock:
             # (the detached aliases keep the storages alive, so their addresses identify them)
             self._d[key] = ((self._ident(vertices), self._ident(faces), H, W), (vertices.detach(), faces.detach()),
-                            gbuffer, saved)
+                            gbuffer, saved, gbuffer._version)
             self._d.move_to_end(key)
             while len(self._d) > 8:
                 self._d.popitem(last=False)
@@ -208,9 +219,12 @@ _geom = _GeomCache()
 
 def set_geometry_sharing(enabled):
     """Turn the shared-geometry cache (renders of one unmodified geometry after the first run the resolve alone) on or
-    off for both implementations of the op; returns the previous setting.  Off: every forward is a full one, as in a
-    training loop whose optimizer changes the vertices each step (tools and benchmarks that repeat one geometry use
-    this to time full steps).  The environment variable DIRT_SHARE_GEOMETRY=0 sets the initial state."""
+    off for both implementations of the op; returns the previous setting.  It is OFF by default -- every forward is a
+    full one -- and opt-in: the environment variable DIRT_SHARE_GEOMETRY=1 sets the initial state to on.  Opting in
+    is a contract: "unmodified" is judged by the tensors' version counters, so while it is on the vertices and faces
+    must only be changed by ops that bump them (any ordinary in-place op does; `v.data.sub_(...)`, a write through a
+    DLPack alias or a raw pointer does not, and the next render would show the old geometry).  A training loop that
+    updates `.data` leaves it off; `shared_geometry()` turns it on for one block of renders."""
     prev = _GeomCache.enabled
     _GeomCache.enabled = bool(enabled)
     if not enabled:
@@ -219,6 +233,25 @@ def set_geometry_sharing(enabled):
     if ext is not None:
         ext.set_geometry_sharing(bool(enabled))
     return prev
+
+
+class shared_geometry:
+    """Context manager for callers that render one geometry several times (samples/deferred.py:63-83: positions,
+    albedo, normals): geometry sharing is on inside the block and restored to its previous setting afterwards.
+
+        with rasterise_ops.shared_geometry():
+            positions = rasterise(bg0, vertices, world_positions, faces)
+            albedo = rasterise(bg1, vertices, vertex_albedo, faces)
+
+    The contract of `set_geometry_sharing(True)` holds inside the block."""
+
+    def __enter__(self):
+        self._prev = set_geometry_sharing(True)
+        return self
+
+    def __exit__(self, *exc):
+        set_geometry_sharing(self._prev)
+        return False
 
 
 def _check_faces_now(faces, B, V, F, stream):

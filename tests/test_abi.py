@@ -91,6 +91,36 @@ def test_zero_batch_is_a_no_op():
                                   0, None, None, None) == _lib.DIRT_OK
 
 
+def _resolve_args(B=1, H=16, W=16, C=3, V=3, F=1, null=(), saved_short=0):
+    """Arguments of dirt_rasterise_fwd_resolve with every pointer set (host words: the checks under test return
+    before any HIP call) except those named in `null`."""
+    saved_b, _ = _lib.workspace_sizes(B, H, W, 3, V, F)
+    word = ctypes.c_uint64(0)
+    p = {k: (None if k in null else ctypes.addressof(word))
+         for k in ("background", "vertex_colors", "gbuffer_in", "saved", "pixels", "gbuffer")}
+    return [p["background"], p["vertex_colors"], B, H, W, C, V, F, p["gbuffer_in"], p["saved"], saved_b - saved_short,
+            p["pixels"], p["gbuffer"], None, None, None], word
+
+
+def test_resolve_validates_without_a_gpu():
+    """dirt_rasterise_fwd_resolve (ABI 13) refuses bad arguments before any HIP call: B == 0 is a no-op, null tensor
+    pointers, a `saved` one byte short of dirt_workspace_sizes() and channel counts outside 1..8 are DIRT_EINVAL."""
+    lib = _lib.load()
+    args, _keep = _resolve_args(B=0, null=("background", "vertex_colors", "gbuffer_in", "saved", "pixels", "gbuffer"))
+    assert lib.dirt_rasterise_fwd_resolve(*args) == _lib.DIRT_OK
+    for name in ("gbuffer_in", "saved", "pixels"):
+        args, _keep = _resolve_args(null=(name,))
+        assert lib.dirt_rasterise_fwd_resolve(*args) == _lib.DIRT_EINVAL, name
+        assert "RasteriseResolve: null tensor pointer" in lib.dirt_last_error().decode(), name
+    args, _keep = _resolve_args(saved_short=1)
+    assert lib.dirt_rasterise_fwd_resolve(*args) == _lib.DIRT_EINVAL
+    assert "saved smaller than" in lib.dirt_last_error().decode()
+    for C in (0, 9):
+        args, _keep = _resolve_args(C=C)
+        assert lib.dirt_rasterise_fwd_resolve(*args) == _lib.DIRT_EINVAL
+        assert "channels" in lib.dirt_last_error().decode()
+
+
 def test_scratch_clear_validates_without_a_gpu():
     lib = _lib.load()
     # B == 0 is a no-op, a too-small scratch is rejected before any HIP call

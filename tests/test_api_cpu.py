@@ -200,3 +200,95 @@ def test_geometry_sharing_switch_cpu():
     finally:
         rasterise_ops.set_geometry_sharing(prev)
 
+
+
+def _sharing_state_in_a_fresh_interpreter(env_value, ext=False):
+    """(_GeomCache.enabled, what set_geometry_sharing(False) returns) of a child interpreter started with
+    DIRT_SHARE_GEOMETRY unset (None) or set to `env_value`; ext: the C++ extension's own flag instead."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "DIRT_SHARE_GEOMETRY"}
+    if env_value is not None:
+        env["DIRT_SHARE_GEOMETRY"] = env_value
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    if ext:
+        code = ("from dirt_amd import rasterise_ops as r; e = r._torch_ext(); assert e is not None; "
+                "a = e.set_geometry_sharing(False); print(a, a)")
+    else:
+        code = "from dirt_amd import rasterise_ops as r; print(r._GeomCache.enabled, r.set_geometry_sharing(False))"
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    return out.stdout.split()[-2:]
+
+
+@pytest.mark.parametrize("env_value,expect", [(None, "False"), ("", "False"), ("0", "False"), ("1", "True")])
+def test_geometry_sharing_is_opt_in_in_a_fresh_interpreter(env_value, expect):
+    """Sharing is off unless DIRT_SHARE_GEOMETRY=1 (or set_geometry_sharing(True)): the state a process starts in,
+    checked in a child interpreter that no test has touched."""
+    assert _sharing_state_in_a_fresh_interpreter(env_value) == [expect, expect]
+
+
+def test_shared_geometry_context_manager():
+    prev = rasterise_ops.set_geometry_sharing(False)
+    try:
+        with rasterise_ops.shared_geometry():
+            assert rasterise_ops._GeomCache.enabled is True
+            with rasterise_ops.shared_geometry():
+                assert rasterise_ops._GeomCache.enabled is True
+            assert rasterise_ops._GeomCache.enabled is True  # the inner block restores the outer's setting
+        assert rasterise_ops._GeomCache.enabled is False
+        with pytest.raises(KeyError):
+            with rasterise_ops.shared_geometry():
+                raise KeyError("x")
+        assert rasterise_ops._GeomCache.enabled is False
+    finally:
+        rasterise_ops.set_geometry_sharing(prev)
+
+
+def test_geometry_cache_never_holds_inference_tensors():
+    """Tensors made under torch.inference_mode() have no version counter (`_version` raises): the cache neither
+    stores nor finds them, and does not raise."""
+    c = rasterise_ops._GeomCache()
+    key = ("dev", 0, 0)
+    gb, saved = torch.zeros(1), torch.zeros(2)
+    v0 = torch.zeros(1, 6, 4)
+    f0 = torch.zeros(1, 2, 3, dtype=torch.int32)
+    with torch.inference_mode():
+        v = torch.arange(24, dtype=torch.float32).reshape(1, 6, 4)
+        f = torch.arange(6, dtype=torch.int32).reshape(1, 2, 3)
+        gbi = torch.zeros(1)
+        assert v.is_inference()
+        with pytest.raises(RuntimeError, match="version counter"):
+            v._version
+        c.store(key, v, f, 8, 8, gb, saved)
+        assert c.find(key, v, f, 8, 8) is None
+        assert len(c._d) == 0
+        # normal geometry rendered inside inference mode: the g-buffer made there is an inference tensor
+        c.store(key, v0, f0, 8, 8, gbi, saved)
+        assert c.find(key, v0, f0, 8, 8) is None
+        # an entry of normal tensors is not served to inference tensors, and a refused store drops it
+        c.store(key, v0, f0, 8, 8, gb, saved)
+        assert c.find(key, v0, f0, 8, 8) == (gb, saved)
+        assert c.find(key, v, f0, 8, 8) is None and c.find(key, v0, f, 8, 8) is None
+        c.store(key, v, f, 8, 8, gb, saved)
+        assert c.find(key, v0, f0, 8, 8) is None
+
+
+def test_geometry_cache_misses_after_the_gbuffer_was_edited():
+    """The cache holds the g-buffer tensor the first forward returned to its caller: an in-place edit of it (its
+    version counter moves) makes the entry a miss."""
+    c = rasterise_ops._GeomCache()
+    key = ("dev", 0, 0)
+    v = torch.zeros(1, 6, 4)
+    f = torch.zeros(1, 2, 3, dtype=torch.int32)
+    gb, saved = torch.zeros(4, dtype=torch.int32), torch.zeros(2)
+    c.store(key, v, f, 8, 8, gb, saved)
+    assert c.find(key, v, f, 8, 8) == (gb, saved)
+    gb.fill_(-1)
+    assert c.find(key, v, f, 8, 8) is None
+    c.store(key, v, f, 8, 8, gb, saved)
+    assert c.find(key, v, f, 8, 8) == (gb, saved)
+    gb.detach()[0] = 3  # through an alias
+    assert c.find(key, v, f, 8, 8) is None

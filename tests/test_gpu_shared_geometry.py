@@ -6,6 +6,10 @@ forward on the same unmodified vertex and face tensors, runs the resolve alone (
 These tests hold such renders to the oracle (pixels bit-exact, gradients in tolerance), count the setup launches to
 show which forwards shared, and check that an in-place change of the geometry, a different tensor with equal values,
 and HIP-graph replays with the geometry changed in place between them all give the results of the new geometry.
+
+Sharing is opt-in: the tests of the cache itself turn it on through the module's autouse fixture; the tests marked
+`_default_state` run with the library as a process finds it (no set_geometry_sharing call, no environment variable)
+and hold the classic optimisation loop -- `v.data.sub_(lr * v.grad)`, which bumps no version counter -- to the oracle.
 """
 import numpy as np
 import pytest
@@ -18,15 +22,36 @@ from test_gpu_parity import assert_close_grad, _gpu
 pytestmark = pytest.mark.gpu
 
 
+def _default_state(fn):
+    """The test runs in the library's default state: the module's fixture leaves the switch alone."""
+    fn._default_state = True
+    return fn
+
+
+@pytest.fixture(autouse=True)
+def _sharing_on(request):
+    """The cache's own tests opt in (set_geometry_sharing(True)), restored afterwards."""
+    if getattr(request.function, "_default_state", False):
+        yield
+        return
+    from dirt_amd import rasterise_ops
+    prev = rasterise_ops.set_geometry_sharing(True)
+    try:
+        yield
+    finally:
+        rasterise_ops.set_geometry_sharing(prev)
+
+
 def _op(impl):
     from dirt_amd import rasterise_ops
     ext = rasterise_ops._torch_ext()
     if impl == "ext":
         assert ext is not None
 
-    def op(bg, v, c, f, H, W, C):
+    def op(bg, v, c, f, H, W, C, with_gbuffer=False):
         args = (bg, v, c, f, None, H, W, C, 0, 0, False, False)
-        return (ext.rasterise(*args) if impl == "ext" else rasterise_ops._RasteriseFunction.apply(*args))[0]
+        outs = ext.rasterise(*args) if impl == "ext" else rasterise_ops._RasteriseFunction.apply(*args)
+        return (outs[0], outs[1]) if with_gbuffer else outs[0]
     return op
 
 
@@ -188,3 +213,109 @@ def test_geometry_sharing_switch(impl):
     finally:
         rasterise_ops.set_geometry_sharing(prev)
 
+
+
+def _render_and_check(op, bt, vt, ct, ft, bg, c, f, dims, gp, what):
+    """One render + backward of the current vertices, held to the oracle (pixels bit-exact, gradients in tolerance)."""
+    H, W, C = dims
+    px = op(bt, vt, ct, ft, H, W, C)
+    gv, gc = torch.autograd.grad(px, [vt, ct], _gpu(gp))
+    vn = vt.detach().cpu().numpy()
+    ref, gb, _ = oracle.rasterise_fwd(bg, vn, c, f)
+    np.testing.assert_array_equal(px.detach().cpu().numpy(), ref, err_msg=what)
+    rgv, rgc, _ = oracle.rasterise_bwd(vn, c, f, ref, gp, gb)
+    assert_close_grad(gc.cpu().numpy(), rgc, "grad_vertex_colors " + what)
+    assert_close_grad(gv.cpu().numpy(), rgv, "grad_vertices " + what)
+    return ref
+
+
+@_default_state
+@pytest.mark.parametrize("impl", ["ext", "py"])
+def test_training_loop_with_data_writes_in_the_default_state(impl):
+    """The classic optimisation loop in the library's default state (no set_geometry_sharing call, no environment
+    variable): `v.data.sub_(...)` and a write through a DLPack alias change the vertices without bumping their
+    version counter, and every render still shows the current geometry, with its gradients.  (With sharing on by
+    default, from step 2 on the op returned the first step's image and gradients.)"""
+    from dirt_amd import rasterise_ops
+    rasterise_ops.workspace_cache_clear(force=True)
+    op = _op(impl)
+    bgs, v, cols, f, dims = _scene()
+    bg, c = bgs[1], cols[1]
+    vt = _gpu(v).requires_grad_(True)
+    ct = _gpu(c).requires_grad_(True)
+    ft, bt = _gpu(f), _gpu(bg)
+    gp = np.random.default_rng(160).standard_normal(bg.shape).astype(np.float32)
+    delta = np.zeros_like(v)
+    delta[0, ::7, :2] = 0.05  # moves every seventh vertex by 4 / 3.2 px: coverage changes
+    first = _render_and_check(op, bt, vt, ct, ft, bg, c, f, dims, gp, "step 1")
+    version = vt._version
+    vt.data.sub_(_gpu(delta))
+    assert vt._version == version, "the write was meant to bypass the version counter"
+    second = _render_and_check(op, bt, vt, ct, ft, bg, c, f, dims, gp, "after v.data.sub_")
+    assert not np.array_equal(first, second), "the step did not move coverage"
+    alias = torch.from_dlpack(torch.utils.dlpack.to_dlpack(vt.detach()))
+    assert alias.data_ptr() == vt.data_ptr()
+    alias.add_(_gpu(2 * delta))
+    assert vt._version == version
+    third = _render_and_check(op, bt, vt, ct, ft, bg, c, f, dims, gp, "after a write through a DLPack alias")
+    assert not np.array_equal(second, third)
+
+
+def test_extension_flag_is_opt_in_in_a_fresh_interpreter():
+    """The C++ op's own switch starts off, and on with DIRT_SHARE_GEOMETRY=1 (a child interpreter: this process's
+    switch has been driven by the tests above)."""
+    from test_api_cpu import _sharing_state_in_a_fresh_interpreter
+    assert _sharing_state_in_a_fresh_interpreter(None, ext=True) == ["False", "False"]
+    assert _sharing_state_in_a_fresh_interpreter("1", ext=True) == ["True", "True"]
+
+
+@pytest.mark.parametrize("impl", ["ext", "py"])
+def test_inference_mode_renders_are_never_shared(impl):
+    """With sharing on: tensors made under torch.inference_mode() track no version counter, so their renders are
+    ineligible -- two renders of the same tensors raise nothing, are the oracle's, and each launches its setup; the
+    same holds for ordinary tensors rendered inside inference mode (the g-buffer made there is an inference tensor)."""
+    from dirt_amd import rasterise_ops
+    assert rasterise_ops._GeomCache.enabled
+    rasterise_ops.workspace_cache_clear(force=True)
+    op = _op(impl)
+    bgs, v, cols, f, (H, W, C) = _scene()
+    ref, _, _ = oracle.rasterise_fwd(bgs[1], v, cols[1], f)
+    v_out, f_out = _gpu(v), _gpu(f)
+    with torch.inference_mode():
+        vt, ft = _gpu(v), _gpu(f)
+        ct, bt = _gpu(cols[1]), _gpu(bgs[1])
+        assert vt.is_inference() and ft.is_inference()
+        for vv, ff in ((vt, ft), (vt, ft), (v_out, f_out), (v_out, f_out)):
+            px, n = _setup_launches(lambda: op(bt, vv, ct, ff, H, W, C))
+            np.testing.assert_array_equal(px.cpu().numpy(), ref)
+            assert n == 1
+    # (outside inference mode the same ordinary tensors share as usual)
+    counts = [_setup_launches(lambda: op(_gpu(bgs[1]), v_out, _gpu(cols[1]), f_out, H, W, C))[1] for _ in range(2)]
+    assert counts == [1, 0]
+
+
+@pytest.mark.parametrize("impl", ["ext", "py"])
+def test_returned_gbuffer_edited_in_place(impl):
+    """With sharing on: the cache holds the g-buffer tensor the first render returned; after the caller overwrites it
+    in place (-1 = background everywhere) the next render of the same geometry is a full one with the oracle's
+    pixels, not a resolve of the edited words."""
+    from dirt_amd import rasterise_ops
+    rasterise_ops.workspace_cache_clear(force=True)
+    op = _op(impl)
+    bgs, v, cols, f, (H, W, C) = _scene()
+    vt, ft = _gpu(v), _gpu(f)
+    ct, bt = _gpu(cols[1]), _gpu(bgs[1])
+    ref, ref_gb, _ = oracle.rasterise_fwd(bgs[1], v, cols[1], f)
+    (px, gb), n = _setup_launches(lambda: op(bt, vt, ct, ft, H, W, C, with_gbuffer=True))
+    assert n == 1
+    np.testing.assert_array_equal(px.cpu().numpy(), ref)
+    np.testing.assert_array_equal(gb.cpu().numpy(), ref_gb)
+    gb.fill_(-1)
+    (px2, gb2), n = _setup_launches(lambda: op(bt, vt, ct, ft, H, W, C, with_gbuffer=True))
+    np.testing.assert_array_equal(px2.cpu().numpy(), ref)
+    np.testing.assert_array_equal(gb2.cpu().numpy(), ref_gb)
+    assert n == 1
+    # the new g-buffer is untouched: the next render shares again
+    px3, n = _setup_launches(lambda: op(bt, vt, ct, ft, H, W, C))
+    np.testing.assert_array_equal(px3.cpu().numpy(), ref)
+    assert n == 0

@@ -86,11 +86,24 @@ def cpu_oracle(host, g, budget_s=3.0):
             "cpu_ms_per_step": round(t * 1e3, 2)}
 
 
-def deferred_chain(steps=20, batched=False):
+def deferred_chain(steps=20, batched=False, share=None):
     """c4 as the reference sample runs it: three 3-channel G-buffer renders + dilation + lighting + loss,
     backward to world-space vertices (tests/deferred_pipeline.py), through dirt_amd.rasterise + autograd.
     Reported eager (host-issued every step), as one captured HIP graph per step (device time: the whole
-    chain replayed, no host work), and the host's issue time alone (eager wall time minus nothing queued)."""
+    chain replayed, no host work), and the host's issue time alone (eager wall time minus nothing queued).
+    The unbatched chain renders one geometry three times: it opts into geometry sharing explicitly (`share`, default
+    on for the unbatched chain; rasterise_ops.set_geometry_sharing, off by default in the library) and says so in its
+    label; share=False times the same chain with every render a full one."""
+    from dirt_amd import rasterise_ops
+    share = (not batched) if share is None else bool(share)
+    prev = rasterise_ops.set_geometry_sharing(share)
+    try:
+        return _deferred_chain(steps, batched, share)
+    finally:
+        rasterise_ops.set_geometry_sharing(prev)
+
+
+def _deferred_chain(steps, batched, share):
     import deferred_pipeline as dp
     dev = torch.device("cuda", 0)
     H = W = 512
@@ -121,7 +134,8 @@ def deferred_chain(steps=20, batched=False):
         step()
     t_issue = (time.perf_counter() - t0) / steps
     torch.cuda.synchronize()
-    res = {"config": "c4_deferred_chain_3x512x512x3_grad_to_world_vertices" + ("_batched" if batched else ""),
+    res = {"config": "c4_deferred_chain_3x512x512x3_grad_to_world_vertices" + ("_batched" if batched else "") +
+           ("_shared_geometry" if share else ""), "geometry_sharing": share,
            "faces": len(faces),
            "ms_per_step_eager": round(dt * 1e3, 3), "host_issue_ms_per_step": round(t_issue * 1e3, 3),
            "Mpixels_per_s_fwd_bwd": round(H * W / dt / 1e6, 1)}
@@ -204,7 +218,8 @@ def main():
         if not sel or any(k in name for k in sel):
             print(json.dumps(run(name, make())), flush=True)
     if not sel or any(k in "c4_deferred_chain" for k in sel):
-        print(json.dumps(deferred_chain()), flush=True)
+        print(json.dumps(deferred_chain()), flush=True)  # (opts into geometry sharing, labelled)
+        print(json.dumps(deferred_chain(share=False)), flush=True)
         print(json.dumps(deferred_chain(batched=True)), flush=True)
 
 
