@@ -10,7 +10,9 @@ kernels (one launch per forward and per backward, dirt_amd/csrc/lighting_kernels
 dirt_vertex_normals_* / dirt_diffuse_directional_* / dirt_specular_directional_* / dirt_diffuse_point_*) when
 their operands are float32 tensors on one GPU, of one [..., 3] shape, with light parameters of shape [3] that need no gradient and a Python-number
 shininess; anything else -- CPU tensors, broadcasting, gradients with respect to the light -- runs the
-framework-op statement below (`_*_ops`), which is also the fused kernels' fp32 test reference.
+framework-op statement below (`_*_ops`).  Both are pinned to the float64 statement in tests/lighting_f64.py;
+a non-finite operand shades alike on either path (NaN propagates through both clamps into the output and the
+colour gradient of its row, and touches no other row).
 
 The fused backwards are kernels, not differentiable graphs: a second-order gradient through them
 (`create_graph=True`) raises RuntimeError rather than silently dropping terms.  DIRT_FUSED_LIGHTING=0 routes every
