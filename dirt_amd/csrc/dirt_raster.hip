@@ -21,8 +21,11 @@
 //                      filter-based dL/dvertices (README.md:146-147) for the gradient contract of
 //                      csrc/rasterise_grad_common.h:19-24.
 //
-// This file holds the shared device helpers, the scratch layout, validation, launches and the C ABI; the
-// three kernels live in the headers named above, included into this one translation unit.
+// This file holds the shared device helpers, the workspace layout and its views, validation and the C ABI; the
+// three kernels live in the headers named above, included into this one translation unit, each followed by its
+// typed launcher (launch_setup / launch_raster / launch_grad): the one function that writes the kernel's <<<>>> and
+// knows its parameter order.  The entry points here fill a RasterLaunch / GradLaunch by field name, pick the channel
+// specialisation with with_channels() and the variant with an if-chain of launcher calls.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -33,6 +36,7 @@
 #include <string.h>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include <algorithm>
@@ -112,7 +116,7 @@ struct Layout {
     int cshift, csize;        // coarse tile edge = 1 << cshift pixels
     int nctx, ncty, ncoarse;  // coarse tiles per frame (<= kMaxCoarse)
     int64_t nrec;
-    size_t saved_recs, saved_fdata, saved_cov, saved_total;
+    size_t saved_fdata, saved_cov, saved_total;  // (the records start `saved`)
     size_t off_count, off_flag, off_bins, scratch_total;
     int64_t bin_capacity;     // entries in all slabs
     uint32_t slab;            // entries per (frame, coarse tile) slab
@@ -169,7 +173,6 @@ int make_layout(int B, int H, int W, int F, int64_t bin_capacity, Layout &L)
     L.bin_capacity = bin_capacity > 0 ? bin_capacity : default_capacity(B, F, L.ncoarse);
     L.slab = (uint32_t)std::min<int64_t>(std::max<int64_t>(L.bin_capacity / slabs, 1), 0x7fffffffLL);
     L.bin_capacity = (int64_t)L.slab * slabs;
-    L.saved_recs = 0;
     L.saved_fdata = (size_t)align_up((int64_t)B * L.nrec * (int64_t)sizeof(Rec), 256);
     L.saved_cov = L.saved_fdata + (size_t)align_up((int64_t)B * F * (int64_t)sizeof(FaceData), 256);
     L.saved_total = L.saved_cov + (size_t)align_up((int64_t)B * H * W, 256);  // 4 coverage bits per pixel
@@ -192,6 +195,74 @@ int validate(int B, int H, int W, int C, int V, int F)
         return fail(DIRT_EINVAL, "Rasterise batch too large (at most 2^26 faces per frame, 2^28 per batch)");
     return DIRT_OK;
 }
+
+// The arrays inside `saved` and `scratch`: Layout offsets applied to a base pointer (const: the readers of `saved`)
+template <class T> T *at(void *base, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
+template <class T> const T *at(const void *base, size_t off) { return at<T>(const_cast<void *>(base), off); }
+struct SavedView {
+    Rec *recs;
+    FaceData *fdata;
+    uint8_t *covbits;
+    SavedView(const Layout &L, void *p)
+        : recs(at<Rec>(p, 0)), fdata(at<FaceData>(p, L.saved_fdata)), covbits(at<uint8_t>(p, L.saved_cov)) {}
+};
+struct ConstSavedView {
+    const Rec *recs;
+    const FaceData *fdata;
+    const uint8_t *covbits;
+    ConstSavedView(const Layout &L, const void *p)
+        : recs(at<Rec>(p, 0)), fdata(at<FaceData>(p, L.saved_fdata)), covbits(at<uint8_t>(p, L.saved_cov)) {}
+};
+struct ScratchView {
+    uint32_t *ccount, *flag;
+    uint2 *bins;
+    ScratchView(const Layout &L, void *p)
+        : ccount(at<uint32_t>(p, L.off_count)), flag(at<uint32_t>(p, L.off_flag)), bins(at<uint2>(p, L.off_bins)) {}
+};
+
+// The compile-time channel specialisation of a run-time C: 1, 3 and 7 have their own, every other count takes the
+// generic one (CC = 0).  Calls fn(std::integral_constant<int, CC>{}).
+template <class Fn>
+void with_channels(int C, Fn &&fn)
+{
+    if (C == 1) fn(std::integral_constant<int, 1>{});
+    else if (C == 3) fn(std::integral_constant<int, 3>{});
+    else if (C == 7) fn(std::integral_constant<int, 7>{});
+    else fn(std::integral_constant<int, 0>{});
+}
+
+// Start / stop events of a timed debug entry point, released on every path out of it.  (ProfScope's events outlive
+// their scope on purpose: dirt_profile_read reads them later.)
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t s = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    hipError_t create()
+    {
+        const hipError_t e = hipEventCreate(&a);
+        return e == hipSuccess ? hipEventCreate(&b) : e;
+    }
+    // create both events and record the first on `stream`
+    hipError_t start(hipStream_t stream)
+    {
+        const hipError_t e = create();
+        return e == hipSuccess ? hipEventRecord(a, s = stream) : e;
+    }
+    // record the second and wait for it; *ms = the time between the two
+    hipError_t stop(float *ms)
+    {
+        hipError_t e = hipEventRecord(b, s);
+        if (e == hipSuccess) e = hipEventSynchronize(b);
+        return e == hipSuccess ? hipEventElapsedTime(ms, a, b) : e;
+    }
+};
 
 #include "setup_kernel.h"
 #include "raster_kernel.h"
@@ -460,18 +531,13 @@ static int rasterise_fwd_impl(const float *background, int tcb, const float *ver
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total)
         return fail(DIRT_EINVAL, "Rasterise: workspace smaller than dirt_workspace_sizes()");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    char *sv = static_cast<char *>(saved), *sc = static_cast<char *>(scratch);
-    Rec *recs = reinterpret_cast<Rec *>(sv + L.saved_recs);
-    FaceData *fdata = reinterpret_cast<FaceData *>(sv + L.saved_fdata);
-    uint8_t *covbits = reinterpret_cast<uint8_t *>(sv + L.saved_cov);
-    uint32_t *ccount = reinterpret_cast<uint32_t *>(sc + L.off_count);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(sc + L.off_flag);
-    uint2 *bins = reinterpret_cast<uint2 *>(sc + L.off_bins);
+    const SavedView sv(L, saved);
+    const ScratchView sc(L, scratch);
 
     // count sets and parity words: one memset, unless the caller vouches that the scratch is clean
     // (DIRT_FWD_SCRATCH_CLEAN: zeroed once and since used only by forwards of the same layout)
     if (!(flags & DIRT_FWD_SCRATCH_CLEAN)) {
-        rc = zero_async(ccount, L.off_bins - L.off_count, stream);
+        rc = zero_async(sc.ccount, L.off_bins - L.off_count, stream);
         if (rc) return rc;
     }
     // small scenes (Gouraud, F <= kFusedMaxF, at most kFusedMaxTiles tiles): the raster sets up the faces itself
@@ -494,7 +560,7 @@ static int rasterise_fwd_impl(const float *background, int tcb, const float *ver
             deep = deep || (last != 0u && next_gen - last <= kDeepRecent);
             if (!capturing) {
                 da->gen = next_gen;
-                DeepScratch &ds = deep_scratch(*da, flag);
+                DeepScratch &ds = deep_scratch(*da, sc.flag);
                 dga.host = da->dev;
                 dga.gen = next_gen;
                 dga.prev_gen = ds.gen;
@@ -506,85 +572,49 @@ static int rasterise_fwd_impl(const float *background, int tcb, const float *ver
     }
     if (F > 0 && !fused) {
         ProfScope ps(K_SETUP, stream);
-        launch_setup<0>(vertices, faces, B, H, W, V, F, L, recs, fdata, ccount, flag, bins, stream, zero_grad_vertices,
-                        (int64_t)B * V * 4, zero_grad_vertex_colors, (int64_t)B * V * C, stash_hdr);
+        launch_setup<0>(vertices, faces, B, H, W, V, F, L, sv, sc, stream, zero_grad_vertices, (int64_t)B * V * 4,
+                        zero_grad_vertex_colors, (int64_t)B * V * C, stash_hdr);
         HIP_TRY(hipGetLastError());
         // (the setup grid's filler workgroups zero the accumulators; the raster does it only when F == 0)
         zero_grad_vertices = nullptr;
         zero_grad_vertex_colors = nullptr;
     }
-    dim3 grid((unsigned)L.ntiles, (unsigned)B);
     ProfScope ps(K_RASTER, stream);
-#define LAUNCH_PROC(CC, SHT)                                                                                     \
-    raster_kernel<CC, 0, SHT><<<grid, dim3(256), 0, stream>>>(                                                   \
-        background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F,                     \
-        tile_grid(L.ntx),                                                                                                     \
-        L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                         \
-        zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                      \
-        zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb)
-#define LAUNCH_RASTER(CC)                                                                                        \
-    if (shader_id == DIRT_SHADER_OCEANIC_HORIZON)                                                                \
-        LAUNCH_PROC(CC, DIRT_SHADER_OCEANIC_HORIZON);                                                            \
-    else if (shader_id == DIRT_SHADER_HILL)                                                                      \
-        LAUNCH_PROC(CC, DIRT_SHADER_HILL);                                                                       \
-    else if (shader_id >= DIRT_SHADER_OCEANIC)                                                                   \
-        LAUNCH_PROC(CC, DIRT_SHADER_OCEANIC);                                                                    \
-    else if (nopix && fused)                                                                                     \
-        raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, false, true, true><<<grid, dim3(256), 0, stream>>>(            \
-            background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), \
-            L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                     \
-            zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                  \
-            zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb, gbo, faces,    \
-            stash_hdr);                                                                                          \
-    else if (nopix)                                                                                              \
-        raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, false, false, true><<<grid, dim3(256), 0, stream>>>(           \
-            background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), \
-            L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                     \
-            zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                  \
-            zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb, gbo, nullptr,  \
-            stash_hdr);                                                                                          \
-    else if (deep && !fused && !want_gb)                                                                         \
-        raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, false, false, false, true><<<grid, dim3(256), 0, stream>>>(     \
-            background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), \
-            L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                     \
-            zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                  \
-            zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb, GbufOut{},      \
-            nullptr, nullptr, dga);                                                                              \
-    else if (fused && want_gb)                                                                                   \
-        raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, true, true><<<grid, dim3(256), 0, stream>>>(                   \
-            background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), \
-            L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                     \
-            zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                  \
-            zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb, gbo, faces);   \
-    else if (fused)                                                                                              \
-        raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, false, true><<<grid, dim3(256), 0, stream>>>(                  \
-            background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), \
-            L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                     \
-            zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                  \
-            zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb, gbo, faces);   \
-    else if (want_gb)                                                                                            \
-        raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, true><<<grid, dim3(256), 0, stream>>>(                         \
-            background, vertex_colors, recs, fdata, ccount, flag, bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), \
-            L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits, zero_grad_vertices,                     \
-            zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                  \
-            zero_grad_vertex_colors ? (int64_t)B * V * C : 0, vertices, camera_pos, shader_id, tcb, gbo);          \
-    else                                                                                                         \
-    raster_kernel<CC><<<grid, dim3(256), 0, stream>>>(background, vertex_colors, recs, fdata, ccount, flag,       \
-                                                      bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx),                     \
-                                                      L.cshift,                                                  \
-                                                      L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits,          \
-                                                      zero_grad_vertices,                                          \
-                                                      zero_grad_vertices ? (int64_t)B * V * 4 : 0,                 \
-                                                      zero_grad_vertex_colors,                                     \
-                                                      zero_grad_vertex_colors ? (int64_t)B * V * C : 0,            \
-                                                      vertices, camera_pos, shader_id, tcb, GbufOut{}, nullptr,    \
-                                                      nullptr, dga)
-    if (C == 1) LAUNCH_RASTER(1);
-    else if (C == 3) LAUNCH_RASTER(3);
-    else if (C == 7) LAUNCH_RASTER(7);
-    else LAUNCH_RASTER(0);
-#undef LAUNCH_RASTER
-#undef LAUNCH_PROC
+    // what every variant takes; the outputs and inputs of one variant alone are set in its branch below
+    RasterLaunch a = raster_launch(L, B, H, W, C, V, F, stream);
+    a.background = background; a.colors = vertex_colors; a.pixels = pixels; a.gbuffer = gbuffer;
+    a.recs = sv.recs; a.fdata = sv.fdata; a.covbits = sv.covbits;
+    a.counts = sc.ccount; a.flag = sc.flag; a.bins = sc.bins; a.slab = L.slab;
+    a.zero_a = zero_grad_vertices; a.zero_b = zero_grad_vertex_colors;
+    a.verts = vertices; a.cam = camera_pos; a.sid = shader_id; a.tcb = tcb;
+    with_channels(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value, G = DIRT_SHADER_GOURAUD;
+        if (shader_id == DIRT_SHADER_OCEANIC_HORIZON) launch_raster<CC, 0, DIRT_SHADER_OCEANIC_HORIZON>(a);
+        else if (shader_id == DIRT_SHADER_HILL) launch_raster<CC, 0, DIRT_SHADER_HILL>(a);
+        else if (shader_id >= DIRT_SHADER_OCEANIC) launch_raster<CC, 0, DIRT_SHADER_OCEANIC>(a);
+        else if (nopix && fused) {
+            a.gbo = gbo; a.faces = faces; a.stash_hdr = stash_hdr;
+            launch_raster<CC, 0, G, false, /*FUSED=*/true, /*NOPIX=*/true>(a);
+        } else if (nopix) {
+            a.gbo = gbo; a.stash_hdr = stash_hdr;
+            launch_raster<CC, 0, G, false, false, /*NOPIX=*/true>(a);
+        } else if (deep && !fused && !want_gb) {
+            a.dga = dga;
+            launch_raster<CC, 0, G, false, false, false, /*OCC=*/true>(a);
+        } else if (fused && want_gb) {
+            a.gbo = gbo; a.faces = faces;
+            launch_raster<CC, 0, G, /*GB=*/true, /*FUSED=*/true>(a);
+        } else if (fused) {
+            a.gbo = gbo; a.faces = faces;
+            launch_raster<CC, 0, G, false, /*FUSED=*/true>(a);
+        } else if (want_gb) {
+            a.gbo = gbo;
+            launch_raster<CC, 0, G, /*GB=*/true>(a);
+        } else {
+            a.dga = dga;
+            launch_raster<CC>(a);
+        }
+    });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }
@@ -631,23 +661,16 @@ int dirt_rasterise_fwd_resolve(const float *background, const float *vertex_colo
     if (rc) return rc;
     if (saved_bytes < L.saved_total) return fail(DIRT_EINVAL, "RasteriseResolve: saved smaller than dirt_workspace_sizes()");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const char *sv = static_cast<const char *>(saved);
-    const Rec *recs = reinterpret_cast<const Rec *>(sv + L.saved_recs);
-    const FaceData *fdata = reinterpret_cast<const FaceData *>(sv + L.saved_fdata);
-    dim3 grid((unsigned)L.ntiles, (unsigned)B);
+    const ConstSavedView sv(L, saved);
     ProfScope ps(K_RASTER, stream);
-#define LAUNCH_RESOLVE(CC)                                                                                         \
-    raster_kernel<CC, 0, DIRT_SHADER_GOURAUD, false, false, false, false, true><<<grid, dim3(256), 0, stream>>>(     \
-        background, vertex_colors, recs, fdata, nullptr, nullptr, nullptr, 0u, B, H, W, C, V, F, tile_grid(L.ntx),   \
-        L.cshift, L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, nullptr, zero_grad_vertices,                        \
-        zero_grad_vertices ? (int64_t)B * V * 4 : 0, zero_grad_vertex_colors,                                     \
-        zero_grad_vertex_colors ? (int64_t)B * V * C : 0, nullptr, nullptr, DIRT_SHADER_GOURAUD, C, GbufOut{},      \
-        nullptr, nullptr, DeepArgs{}, gbuffer_in)
-    if (C == 1) LAUNCH_RESOLVE(1);
-    else if (C == 3) LAUNCH_RESOLVE(3);
-    else if (C == 7) LAUNCH_RESOLVE(7);
-    else LAUNCH_RESOLVE(0);
-#undef LAUNCH_RESOLVE
+    // (no bins, counts, coverage bits, vertices or camera: the visible record comes from gbuffer_in)
+    RasterLaunch a = raster_launch(L, B, H, W, C, V, F, stream);
+    a.background = background; a.colors = vertex_colors; a.pixels = pixels; a.gbuffer = gbuffer;
+    a.recs = sv.recs; a.fdata = sv.fdata; a.gb_in = gbuffer_in;
+    a.zero_a = zero_grad_vertices; a.zero_b = zero_grad_vertex_colors;
+    with_channels(C, [&](auto cc) {
+        launch_raster<decltype(cc)::value, 0, DIRT_SHADER_GOURAUD, false, false, false, false, /*RESOLVE=*/true>(a);
+    });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }
@@ -662,12 +685,15 @@ int dirt_hill_fwd(const float *terrain, int terrain_channels, const float *verti
                               bin_capacity, 0u, nullptr, nullptr, stream_);
 }
 
-static NdcScale ndc_scale(int W, int H)
-{
-    return NdcScale{2.0f / (float)W, 2.0f / (float)H, 0.5f * (float)W, 0.5f * (float)H};
-}
-
 }  // extern "C"
+
+// dirt_debug_bwd_variant's ablation AB of the backward (C == 3 or 7, both gradients)
+template <int AB>
+static void launch_grad_3or7(const GradLaunch &g)
+{
+    if (g.C == 3) launch_grad<3, AB>(g);
+    else launch_grad<7, AB>(g);
+}
 
 // the backward of dirt_rasterise_bwd; stash_flip: the recompute workspace's stash parity (flipped by the launch)
 static int rasterise_bwd_impl(const float *vertices, const float *vertex_colors, const int32_t *faces,
@@ -689,10 +715,6 @@ static int rasterise_bwd_impl(const float *vertices, const float *vertex_colors,
     rc = make_layout(B, H, W, F, 0, L);
     if (rc) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const char *sv = static_cast<const char *>(saved);
-    const Rec *recs = reinterpret_cast<const Rec *>(sv + L.saved_recs);
-    const FaceData *fdata = reinterpret_cast<const FaceData *>(sv + L.saved_fdata);
-    const uint8_t *covbits = reinterpret_cast<const uint8_t *>(sv + L.saved_cov);
     // which gradients to produce: a null grad_vertices / grad_vertex_colors is not computed at all (GM bits)
     const int gm = (grad_vertices ? 1 : 0) | (grad_vertex_colors ? 2 : 0);
     if (V > 0 && !(flags & DIRT_BWD_ACCUMULATE)) {
@@ -712,27 +734,17 @@ static int rasterise_bwd_impl(const float *vertices, const float *vertex_colors,
             return DIRT_OK;
         }
     }
-    // backward tiles: kGradTileW x grad_tile_h(C) (grad_kernel.h)
-    const int gntx = (W + kGradTileW - 1) / kGradTileW, gnty = (H + grad_tile_h(C) - 1) / grad_tile_h(C);
-    dim3 grid((unsigned)(gntx * gnty), (unsigned)B);
     ProfScope ps(K_GRAD, stream);
-#define LAUNCH_GRAD_GM(CC, GMV)                                                                              \
-    grad_kernel<CC, 0, kGradTileW, grad_tile_h(CC), GMV><<<grid, dim3(GradGeom<kGradTileW, grad_tile_h(CC)>::NT), 0, \
-                                                          stream>>>(                                            \
-        pixels, grad_pixels, gbuffer, covbits, recs, fdata, B, H, W, C, V, F, tile_grid(gntx), L.nrec,          \
-        grad_vertices, grad_vertex_colors, grad_background, ndc_scale(W, H), stash_flip)
-#define LAUNCH_GRAD(CC)                                                                                       \
-    do {                                                                                                      \
-        if (gm == 1) LAUNCH_GRAD_GM(CC, 1);                                                                   \
-        else if (gm == 2) LAUNCH_GRAD_GM(CC, 2);                                                              \
-        else LAUNCH_GRAD_GM(CC, 3);                                                                           \
-    } while (0)
-    if (C == 1) LAUNCH_GRAD(1);
-    else if (C == 3) LAUNCH_GRAD(3);
-    else if (C == 7) LAUNCH_GRAD(7);
-    else LAUNCH_GRAD(0);
-#undef LAUNCH_GRAD
-#undef LAUNCH_GRAD_GM
+    GradLaunch g = grad_launch(L, saved, B, H, W, C, V, F, stream);
+    g.pixels = pixels; g.grad_pixels = grad_pixels; g.gbuffer = gbuffer;
+    g.grad_verts = grad_vertices; g.grad_colors = grad_vertex_colors; g.grad_bg = grad_background;
+    g.stash_flip = stash_flip;
+    with_channels(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value;
+        if (gm == 1) launch_grad<CC, 0, 1>(g);
+        else if (gm == 2) launch_grad<CC, 0, 2>(g);
+        else launch_grad<CC, 0, 3>(g);
+    });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }
@@ -935,7 +947,7 @@ int dirt_debug_clip_stats(int B, int H, int W, int F, int64_t bin_capacity, void
     if (rc) return rc;
     if (!scratch || scratch_bytes < L.scratch_total) return fail(DIRT_EINVAL, "dirt_debug_clip_stats: scratch too small");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + L.off_flag);
+    uint32_t *flag = ScratchView(L, scratch).flag;
     uint32_t h[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&h[0], flag + kStatCapCulled, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(&h[1], flag + kStatClamped, 4, hipMemcpyDeviceToHost, stream));
@@ -1000,41 +1012,29 @@ int dirt_debug_raster_variant(int variant, const float *background, const float 
     int rc = make_layout(B, H, W, F, 0, L);
     if (rc) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    char *sv = static_cast<char *>(saved), *sc = static_cast<char *>(scratch);
-    Rec *recs = reinterpret_cast<Rec *>(sv + L.saved_recs);
-    FaceData *fdata = reinterpret_cast<FaceData *>(sv + L.saved_fdata);
-    uint8_t *covbits = reinterpret_cast<uint8_t *>(sv + L.saved_cov);
-    uint32_t *ccount = reinterpret_cast<uint32_t *>(sc + L.off_count);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(sc + L.off_flag);
-    uint2 *bins = reinterpret_cast<uint2 *>(sc + L.off_bins);
+    const SavedView sv(L, saved);
+    const ScratchView sc(L, scratch);
     // re-bin from a clean scratch, then time the raster variant alone
-    HIP_TRY(hipMemsetAsync(ccount, 0, L.off_bins - L.off_count, stream));
-    if (F > 0) launch_setup<0>(vertices, faces, B, H, W, V, F, L, recs, fdata, ccount, flag, bins, stream);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, stream));
-    dim3 grid((unsigned)L.ntiles, (unsigned)B);
-#define V_RAST(AB)                                                                                                 \
-    case AB:                                                                                                       \
-        raster_kernel<3, AB><<<grid, dim3(256), 0, stream>>>(background, vertex_colors, recs, fdata, ccount, flag,    \
-                                                             bins, L.slab, B, H, W, C, V, F, tile_grid(L.ntx), L.cshift,         \
-                                                             L.nctx, L.ncoarse, L.nrec, pixels, gbuffer, covbits,     \
-                                                             nullptr, 0,                                              \
-                                                             nullptr, 0, nullptr, nullptr, 0, C);                    \
-        break
+    HIP_TRY(hipMemsetAsync(sc.ccount, 0, L.off_bins - L.off_count, stream));
+    if (F > 0) launch_setup<0>(vertices, faces, B, H, W, V, F, L, sv, sc, stream);
+    RasterLaunch a = raster_launch(L, B, H, W, C, V, F, stream);
+    a.background = background; a.colors = vertex_colors; a.pixels = pixels; a.gbuffer = gbuffer;
+    a.recs = sv.recs; a.fdata = sv.fdata; a.covbits = sv.covbits;
+    a.counts = sc.ccount; a.flag = sc.flag; a.bins = sc.bins; a.slab = L.slab;
+    EventPair ev;
+    HIP_TRY(ev.start(stream));
     switch (variant) {
-        V_RAST(0); V_RAST(1); V_RAST(2); V_RAST(4); V_RAST(8); V_RAST(32); V_RAST(64); V_RAST(96); V_RAST(128); V_RAST(512); V_RAST(1024); V_RAST(2048);
+    case 0: launch_raster<3, 0>(a); break;        case 1: launch_raster<3, 1>(a); break;
+    case 2: launch_raster<3, 2>(a); break;        case 4: launch_raster<3, 4>(a); break;
+    case 8: launch_raster<3, 8>(a); break;        case 32: launch_raster<3, 32>(a); break;
+    case 64: launch_raster<3, 64>(a); break;      case 96: launch_raster<3, 96>(a); break;
+    case 128: launch_raster<3, 128>(a); break;    case 512: launch_raster<3, 512>(a); break;
+    case 1024: launch_raster<3, 1024>(a); break;  case 2048: launch_raster<3, 2048>(a); break;
     default:
         return fail(DIRT_EINVAL, "dirt_debug_raster_variant: unknown variant");
     }
-#undef V_RAST
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIP_TRY(ev.stop(ms));
     return DIRT_OK;
 }
 
@@ -1048,33 +1048,23 @@ int dirt_debug_setup_ts(int variant, const float *vertices, const int32_t *faces
     int rc = make_layout(B, H, W, F, 0, L);
     if (rc) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    char *sv = static_cast<char *>(saved), *sc = static_cast<char *>(scratch);
-    Rec *recs = reinterpret_cast<Rec *>(sv + L.saved_recs);
-    FaceData *fdata = reinterpret_cast<FaceData *>(sv + L.saved_fdata);
-    uint32_t *ccount = reinterpret_cast<uint32_t *>(sc + L.off_count);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(sc + L.off_flag);
-    uint2 *bins = reinterpret_cast<uint2 *>(sc + L.off_bins);
-    HIP_TRY(hipMemsetAsync(ccount, 0, L.off_bins - L.off_count, stream));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, stream));
+    const SavedView sv(L, saved);
+    const ScratchView sc(L, scratch);
+    HIP_TRY(hipMemsetAsync(sc.ccount, 0, L.off_bins - L.off_count, stream));
+    EventPair ev;
+    HIP_TRY(ev.start(stream));
+    // variant -> setup_kernel's AB
+    auto run = [&](auto ab) { launch_setup<decltype(ab)::value>(vertices, faces, B, H, W, V, F, L, sv, sc, stream); };
     switch (variant) {
-#define V_SETUP(K, AB)                                                                                        \
-    case K:                                                                                                   \
-        launch_setup<AB>(vertices, faces, B, H, W, V, F, L, recs, fdata, ccount, flag, bins, stream);         \
-        break
-        V_SETUP(0, 128); V_SETUP(1, 129); V_SETUP(2, 0); V_SETUP(3, 1); V_SETUP(4, 2); V_SETUP(5, 3); V_SETUP(6, 4);
-#undef V_SETUP
+    case 0: run(std::integral_constant<int, 128>{}); break;  case 1: run(std::integral_constant<int, 129>{}); break;
+    case 2: run(std::integral_constant<int, 0>{}); break;    case 3: run(std::integral_constant<int, 1>{}); break;
+    case 4: run(std::integral_constant<int, 2>{}); break;    case 5: run(std::integral_constant<int, 3>{}); break;
+    case 6: run(std::integral_constant<int, 4>{}); break;
     default:
         return fail(DIRT_EINVAL, "dirt_debug_setup_ts: unknown variant");
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIP_TRY(ev.stop(ms));
     return DIRT_OK;
 }
 
@@ -1089,43 +1079,26 @@ int dirt_debug_bwd_variant(int variant, const float *pixels, const float *grad_p
     int rc = make_layout(B, H, W, F, 0, L);
     if (rc) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const char *sv = static_cast<const char *>(saved);
-    const Rec *recs = reinterpret_cast<const Rec *>(sv + L.saved_recs);
-    const FaceData *fdata = reinterpret_cast<const FaceData *>(sv + L.saved_fdata);
-    const uint8_t *covbits = reinterpret_cast<const uint8_t *>(sv + L.saved_cov);
     HIP_TRY(hipMemsetAsync(grad_vertices, 0, (size_t)B * V * 4 * sizeof(float), stream));
     HIP_TRY(hipMemsetAsync(grad_vertex_colors, 0, (size_t)B * V * C * sizeof(float), stream));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, stream));
-    const int gntx = (W + kGradTileW - 1) / kGradTileW, gnty = (H + grad_tile_h(C) - 1) / grad_tile_h(C);
-    dim3 grid((unsigned)(gntx * gnty), (unsigned)B), blk(C == 3 ? GradGeom<kGradTileW, grad_tile_h(3)>::NT
-                                                                : GradGeom<kGradTileW, grad_tile_h(7)>::NT);
-#define V_GRAD(AB)                                                                                                   \
-    case AB:                                                                                                         \
-        if (C == 3)                                                                                                  \
-            grad_kernel<3, AB><<<grid, blk, 0, stream>>>(pixels, grad_pixels, gbuffer, covbits, recs, fdata, B,       \
-                                                         H, W, C, V, F, tile_grid(gntx), L.nrec, grad_vertices,       \
-                                                         grad_vertex_colors, grad_background, ndc_scale(W, H));       \
-        else                                                                                                         \
-            grad_kernel<7, AB><<<grid, blk, 0, stream>>>(pixels, grad_pixels, gbuffer, covbits, recs, fdata, B,       \
-                                                         H, W, C, V, F, tile_grid(gntx), L.nrec, grad_vertices,       \
-                                                         grad_vertex_colors, grad_background, ndc_scale(W, H));       \
-        break
+    GradLaunch g = grad_launch(L, saved, B, H, W, C, V, F, stream);
+    g.pixels = pixels; g.grad_pixels = grad_pixels; g.gbuffer = gbuffer;
+    g.grad_verts = grad_vertices; g.grad_colors = grad_vertex_colors; g.grad_bg = grad_background;
+    EventPair ev;
+    HIP_TRY(ev.start(stream));
     switch (variant) {
-        V_GRAD(0); V_GRAD(1); V_GRAD(2); V_GRAD(3); V_GRAD(4); V_GRAD(5); V_GRAD(8); V_GRAD(16); V_GRAD(7);
-        V_GRAD(32); V_GRAD(64); V_GRAD(72); V_GRAD(128); V_GRAD(256);
+    case 0: launch_grad_3or7<0>(g); break;      case 1: launch_grad_3or7<1>(g); break;
+    case 2: launch_grad_3or7<2>(g); break;      case 3: launch_grad_3or7<3>(g); break;
+    case 4: launch_grad_3or7<4>(g); break;      case 5: launch_grad_3or7<5>(g); break;
+    case 7: launch_grad_3or7<7>(g); break;      case 8: launch_grad_3or7<8>(g); break;
+    case 16: launch_grad_3or7<16>(g); break;    case 32: launch_grad_3or7<32>(g); break;
+    case 64: launch_grad_3or7<64>(g); break;    case 72: launch_grad_3or7<72>(g); break;
+    case 128: launch_grad_3or7<128>(g); break;  case 256: launch_grad_3or7<256>(g); break;
     default:
         return fail(DIRT_EINVAL, "dirt_debug_bwd_variant: unknown variant");
     }
-#undef V_GRAD
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIP_TRY(ev.stop(ms));
     return DIRT_OK;
 }
 
@@ -1147,30 +1120,20 @@ int dirt_debug_bwd_dispatch_ms(const float *pixels, const float *grad_pixels, co
     rc = make_layout(B, H, W, F, 0, L);
     if (rc) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const char *sv = static_cast<const char *>(saved);
-    const Rec *recs = reinterpret_cast<const Rec *>(sv + L.saved_recs);
-    const FaceData *fdata = reinterpret_cast<const FaceData *>(sv + L.saved_fdata);
-    const uint8_t *covbits = reinterpret_cast<const uint8_t *>(sv + L.saved_cov);
-    const int gntx = (W + kGradTileW - 1) / kGradTileW, gnty = (H + grad_tile_h(3) - 1) / grad_tile_h(3);
-    const dim3 grid((unsigned)(gntx * gnty), (unsigned)B), blk(GradGeom<kGradTileW, grad_tile_h(3)>::NT);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
+    GradLaunch g = grad_launch(L, saved, B, H, W, C, V, F, stream);
+    g.pixels = pixels; g.grad_pixels = grad_pixels; g.gbuffer = gbuffer;
+    g.grad_verts = grad_vertices; g.grad_colors = grad_vertex_colors; g.grad_bg = grad_background;
+    EventPair ev;
+    hipError_t err = ev.create();
     float total = 0.0f;
     for (int r = 0; r < reps && err == hipSuccess; ++r) {
-        hipExtLaunchKernelGGL(grad_kernel<3, 0, kGradTileW, grad_tile_h(3), 3>, grid, blk, 0u, stream, e0, e1, 0u,
-                              pixels, grad_pixels, gbuffer, covbits, recs, fdata, B, H, W, C, V, F, tile_grid(gntx),
-                              L.nrec, grad_vertices, grad_vertex_colors, grad_background, ndc_scale(W, H),
-                              static_cast<uint32_t *>(nullptr));
+        launch_grad<3, 0, 3>(g, ev.a, ev.b);
         err = hipGetLastError();
-        if (err == hipSuccess) err = hipEventSynchronize(e1);
+        if (err == hipSuccess) err = hipEventSynchronize(ev.b);
         float t = 0.0f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+        if (err == hipSuccess) err = hipEventElapsedTime(&t, ev.a, ev.b);
         total += t;
     }
-    // (the events are released on every path)
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     HIP_TRY(err);
     *ms = total / (float)reps;
     return DIRT_OK;

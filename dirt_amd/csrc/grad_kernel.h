@@ -273,7 +273,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GradGeom<TWX, TH>::NT),
                                                    const FaceData *__restrict__ fdata, int B, int H, int W, int Cdyn,
                                                    int V, int F, TileGrid tg, int64_t nrec, float *__restrict__ grad_verts,
                                                    float *__restrict__ grad_colors, float *__restrict__ grad_bg,
-                                                   const NdcScale ns, uint32_t *__restrict__ stash_flip = nullptr)
+                                                   const NdcScale ns, uint32_t *__restrict__ stash_flip)
 {    // recompute backward: flip the gradient stash's parity for the next call (dirt_raster.hip stash_check_kernel)
     if (stash_flip != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) stash_flip[0] ^= 1u;
 
@@ -286,10 +286,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GradGeom<TWX, TH>::NT),
     constexpr int NVM = kNVV + ((GM & 2) ? 3 * CM : 0);
     const int C = CC > 0 ? CC : Cdyn;
     const int NV = kNVV + ((GM & 2) ? 3 * C : 0);
-#if defined(DIRT_GRAD_LDS_PAD) && DIRT_GRAD_LDS_PAD > 0
-    __shared__ volatile char occupancy_probe[DIRT_GRAD_LDS_PAD];  // experiment: caps workgroups per CU
-    if (threadIdx.x == 1023) occupancy_probe[0] = 0;
-#endif
     // RGB (kPacked): one 32-B record per staged pixel, {G.xyz, g-buffer word} and {I.xyz, coverage bits}, the two
     // 16-B halves swapped on odd region rows.  A neighbour's operands are then two ds_read_b128 (4 LDS cycles each,
     // conflict-free over every lane group for the own pixel and its four neighbours) instead of two ds_read_b96
@@ -299,12 +295,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GradGeom<TWX, TH>::NT),
     constexpr bool kPacked = CM == 3;
     __shared__ int32_t s_gb[kPacked ? 1 : kHaloPix];
     __shared__ uint8_t s_cov[kPacked ? 1 : kHaloPix];  // neighbour_coverage() bits of the pixel's face (forward)
-#ifndef DIRT_GRAD_PAIR_RECOMPUTE
-#define DIRT_GRAD_PAIR_RECOMPUTE 1
-#endif
     // RGB: each lane recomputes the pair scalars of its four pairs in phase B instead of staging them
     // (LDS 22 -> 19 KiB: 8 workgroups per CU instead of 7); other channel counts stage them in phase A
-    constexpr bool kRecompute = DIRT_GRAD_PAIR_RECOMPUTE && CM == 3;
+    constexpr bool kRecompute = CM == 3;
     __shared__ float s_sx[kRecompute ? 1 : kHaloPix];  // pair scalar s of (k, k+x) and (k, k+y), DESIGN.md 4
     __shared__ float s_sy[kRecompute ? 1 : kHaloPix];
     // G / I of the staged pixels (phases A-B), then reused for the run-tail partial sums (C-D):
@@ -860,4 +853,52 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GradGeom<TWX, TH>::NT),
         __syncthreads();
         PHASE_TS(7);
     }
+}
+
+// Everything one backward launch takes, by name (recs / fdata / covbits: the forward's `saved`).
+struct GradLaunch {
+    hipStream_t stream;
+    int B, H, W, C, V, F;
+    int64_t nrec;
+    const Rec *recs;
+    const FaceData *fdata;
+    const uint8_t *covbits;
+    const float *pixels = nullptr, *grad_pixels = nullptr;
+    const int32_t *gbuffer = nullptr;
+    float *grad_verts = nullptr, *grad_colors = nullptr, *grad_bg = nullptr;
+    uint32_t *stash_flip = nullptr;  // the recompute workspace's stash parity (flipped by the launch)
+};
+
+// the sizes and the forward's `saved`; the caller sets the tensors
+inline GradLaunch grad_launch(const Layout &L, const void *saved, int B, int H, int W, int C, int V, int F,
+                              hipStream_t stream)
+{
+    const ConstSavedView sv(L, saved);
+    GradLaunch g;
+    g.stream = stream; g.nrec = L.nrec;
+    g.B = B; g.H = H; g.W = W; g.C = C; g.V = V; g.F = F;
+    g.recs = sv.recs; g.fdata = sv.fdata; g.covbits = sv.covbits;
+    return g;
+}
+
+// The one place that launches grad_kernel, and so the one place that knows its parameter order, its tiles
+// (kGradTileW x grad_tile_h(C)) and the window-transform constants.  With a start / stop event pair the launch goes
+// through hipExtLaunchKernelGGL, which takes the events' times from the dispatch itself
+// (dirt_debug_bwd_dispatch_ms).
+template <int CC, int AB = 0, int GM = 3>
+void launch_grad(const GradLaunch &g, hipEvent_t start = nullptr, hipEvent_t stop = nullptr)
+{
+    constexpr int TH = grad_tile_h(CC);
+    const int gntx = (g.W + kGradTileW - 1) / kGradTileW, gnty = (g.H + TH - 1) / TH;
+    const dim3 grid((unsigned)(gntx * gnty), (unsigned)g.B), blk(GradGeom<kGradTileW, TH>::NT);
+    const NdcScale ns{2.0f / (float)g.W, 2.0f / (float)g.H, 0.5f * (float)g.W, 0.5f * (float)g.H};
+    auto go = [&](auto... args) {
+        if (start)
+            hipExtLaunchKernelGGL(grad_kernel<CC, AB, kGradTileW, TH, GM>, grid, blk, 0u, g.stream, start, stop, 0u,
+                                  args...);
+        else
+            grad_kernel<CC, AB, kGradTileW, TH, GM><<<grid, blk, 0, g.stream>>>(args...);
+    };
+    go(g.pixels, g.grad_pixels, g.gbuffer, g.covbits, g.recs, g.fdata, g.B, g.H, g.W, g.C, g.V, g.F, tile_grid(gntx),
+       g.nrec, g.grad_verts, g.grad_colors, g.grad_bg, ns, g.stash_flip);
 }

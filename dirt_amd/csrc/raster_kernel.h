@@ -17,15 +17,12 @@
 // Results are bit-identical to R3/R4 (oracle) by construction.
 
 constexpr int kStrips = 4;
-// The pixels a wave owns inside its 16x16 tile: an 8x8 block (DIRT_RASTER_STRIPS=0, default) or a 16x4
-// strip.  A block is the more compact shape: fewer triangles overlap it (Steiner: the overlap area of a
-// region and a triangle grows with the region's perimeter, 32 vs 40 px), so fewer entries per wave.
-#ifndef DIRT_RASTER_STRIPS
-#define DIRT_RASTER_STRIPS 0
-#endif
-constexpr int kWaveW = DIRT_RASTER_STRIPS ? 16 : 8, kWaveH = DIRT_RASTER_STRIPS ? 4 : 8;
-__host__ __device__ constexpr int wave_ox(int w) { return DIRT_RASTER_STRIPS ? 0 : 8 * (w & 1); }
-__host__ __device__ constexpr int wave_oy(int w) { return DIRT_RASTER_STRIPS ? 4 * w : 8 * (w >> 1); }
+// The pixels a wave owns inside its 16x16 tile: an 8x8 block.  A block is a more compact shape than a 16x4 strip:
+// fewer triangles overlap it (Steiner: the overlap area of a region and a triangle grows with the region's
+// perimeter, 32 vs 40 px), so fewer entries per wave.
+constexpr int kWaveW = 8, kWaveH = 8;
+__host__ __device__ constexpr int wave_ox(int w) { return 8 * (w & 1); }
+__host__ __device__ constexpr int wave_oy(int w) { return 8 * (w >> 1); }
 // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 shares an L2),
 // so give each residue class a contiguous band of tiles; neighbouring tiles then share halo pixels and
 // records in one L2.  A bijection on [0, n); speed only, never correctness.
@@ -55,16 +52,10 @@ static_assert((DIRT_MAX_DIM / kTile) <= 512 && (DIRT_MAX_DIM / kTile) * (DIRT_MA
               "TileGrid reciprocal range");
 inline TileGrid tile_grid(int ntx) { return TileGrid{ntx, (uint32_t)(((1ull << 31) + (uint64_t)ntx - 1) / (uint64_t)ntx)}; }
 
-#ifndef DIRT_RASTER_LISTS
-#define DIRT_RASTER_LISTS 1  // per-wave entry lists (1) or the scalar bit-mask walk (0)
-#endif
 // Hierarchical depth culling (depth-tested programs): a wave whose list holds at least DIRT_RASTER_HZ_MIN
 // entries walks it in groups of 16 and skips every entry whose depth lower bound over the tile exceeds
 // the farthest depth its 64 pixels already hold -- such an entry can win no pixel.  Pays where depth
 // complexity is high (large overlapping triangles); short lists keep the plain loop.
-#ifndef DIRT_RASTER_HZ
-#define DIRT_RASTER_HZ 1
-#endif
 #ifndef DIRT_RASTER_HZ_MIN
 #define DIRT_RASTER_HZ_MIN 32
 #endif
@@ -92,9 +83,6 @@ constexpr int kDotEdge = 1 << 15;
 constexpr uint32_t kLargeAB = 0x80008000u;  // ab[0] of a large entry (A = B = -2^15 never occurs in a small one)
 // the resolve's int32 path: winners with every |A|, |B| < 2^14 (see the resolve)
 constexpr int32_t kResolveSmall = 1 << 14;
-#ifndef DIRT_RASTER_RESOLVE32
-#define DIRT_RASTER_RESOLVE32 1
-#endif
 
 struct alignas(16) StripEntry {  // 48 B of wave-private LDS per staged (sub-)triangle: three ds_read_b128
     int32_t e[3];    // small: E + owned at the strip origin (2^30 when the edge holds over the whole strip);
@@ -256,7 +244,6 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
     return max(max(a, b), max(c, d));
 }
 
-#if DIRT_RASTER_HZ
 // Conservative lower bound of the quantised depth a staged small entry can reach in the wave's pixel
 // rectangle at (x0, y0): the plane's minimum over the rectangle is at the corner its slopes point away
 // from; every zw the raster computes is within 2^-23 (|za||dx| + |zb||dy| + |z0|) of the exact plane
@@ -274,7 +261,6 @@ __device__ __forceinline__ uint32_t entry_qmin(const StripEntry *ent, uint32_t o
     const float zq = __builtin_fmaf(__builtin_fmaf(-s, 0x1p-21f, zc), 16777215.0f, -2.0f);
     return zq > 0.0f ? (uint32_t)fminf(zq, 16777215.0f) : 0u;
 }
-#endif
 
 // Occluder bound (DIRT_RASTER_OCC): a staged small entry that covers the wave's whole 8x8 block (all four
 // corner pixel centres inside -- the block is convex) with its depth inside [0, 1) there writes or beats every
@@ -535,11 +521,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                                                      float *__restrict__ zero_a,
                                                      int64_t nzero_a, float *__restrict__ zero_b, int64_t nzero_b,
                                                      const float *__restrict__ verts, const float *__restrict__ cam,
-                                                     int sid, int tcb, GbufOut gbo = GbufOut{},
-                                                     const int32_t *__restrict__ faces = nullptr,
-                                                     const uint32_t *__restrict__ stash_hdr = nullptr,
-                                                     const DeepArgs dga = DeepArgs{},
-                                                     const int32_t *__restrict__ gb_in = nullptr)
+                                                     int sid, int tcb, GbufOut gbo,
+                                                     const int32_t *__restrict__ faces,
+                                                     const uint32_t *__restrict__ stash_hdr, const DeepArgs dga,
+                                                     const int32_t *__restrict__ gb_in)
 {
     constexpr bool kNoDepth = SH == DIRT_SHADER_HILL;
     static_assert(!(GB && kNoDepth), "hill has no depth buffer");
@@ -552,10 +537,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     // FUSED: the frame's records and FaceData, set up in LDS by this workgroup
     __shared__ Rec s_recs[FUSED ? (1 + kExtraPerFace) * kFusedMaxF : 1];
     __shared__ FaceData s_fd[FUSED ? kFusedMaxF : 1];
-#if defined(DIRT_RASTER_LDS_PAD) && DIRT_RASTER_LDS_PAD > 0
-    __shared__ volatile char occupancy_probe[DIRT_RASTER_LDS_PAD];  // experiment: caps workgroups per CU
-    if (threadIdx.x == 1023) occupancy_probe[0] = 0;
-#endif
     PHASE_TS(0);
     constexpr int CM = CC > 0 ? CC : DIRT_MAX_CHANNELS;
     const int C = CC > 0 ? CC : Cdyn;
@@ -563,7 +544,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     __shared__ int32_t t_nw[2][kStrips];                // segment lengths, double-buffered by chunk parity
     __shared__ StripEntry t_ent[257];                   // one staging round: an entry per thread (+ sentinel)
     __shared__ uint8_t t_mask[256];                     // strips the entry can cover; bit 4: large
-#if DIRT_RASTER_LISTS
     // per-wave entry lists of a staging round: byte offsets into t_ent of the small entries from the
     // front (padded to even with the sentinel), indices of the large ones from the back
     __shared__ uint32_t t_wl[kStrips][kWaveList];
@@ -574,7 +554,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
         d[1] = make_int4(0, 0, 0, 0);
         d[2] = make_int4(0, 0, 0, 0);
     }
-#endif
     // Gouraud: XCD bands (L2 sharing of bins / records between neighbouring tiles); a procedural
     // program is compute-bound and its cost follows the image content (sky vs water), so its tiles are
     // interleaved over the XCDs instead (round-robin dispatch order) for balance
@@ -770,7 +749,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                 __syncthreads();
                 if (chunk == 0 && from == 0) PHASE_TS(2);
                 const int nst = min(256, n_list - from);
-#if DIRT_RASTER_LISTS
                 if (!(AB & 1)) {
                     // this wave's entries as a list (ballot compaction of the round's masks): the loop then
                     // walks offsets read two at a time instead of scanning a bit mask on the scalar unit
@@ -795,25 +773,21 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                     // tested (reads at k + 2 <= ns + 1 stay inside the list)
                     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
                     typedef const volatile __attribute__((address_space(3))) u32x2 lds_u32x2;
-                    // Depth-tested programs with long lists (DIRT_RASTER_HZ): the list runs in segments -- the
-                    // first DIRT_RASTER_HZ_MIN entries as they are, then each following group of 64 compacted in
+                    // Depth-tested programs with long lists (hierarchical depth culling): the list runs in segments --
+                    // the first DIRT_RASTER_HZ_MIN entries as they are, then each following group of 64 compacted in
                     // place (to its front) to the entries whose depth lower bound over the tile does not exceed
                     // the farthest depth the wave's pixels hold; the others can win no pixel.  A segment starts
                     // even (aligned pair reads); the second read of an odd segment's last pair lands on a
                     // valid entry (stale or next) or the sentinel, and an entry run twice changes nothing (min).
-#if DIRT_RASTER_HZ
                     if (OCC && !kNoDepth && ns > DIRT_RASTER_OCC_MIN)
                         // (readfirstlane: the call returns in a VGPR, and a divergent-looking ns would turn the
                         // list walks' uniform loop control into exec-masked vector code)
                         ns = __builtin_amdgcn_readfirstlane(
                             occluder_cull(t_ent, t_wl[wave], ns, wave_ox(wave), wave_oy(wave), ti0, tj0));
-#endif
                     int base = 0;
                     // (a long list -- large overlapping faces -- runs only DIRT_RASTER_HZ_DEEP entries before its
                     // first cull: they cover the block, and the cull drops most of the rest)
-                    int seg = (!kNoDepth && DIRT_RASTER_HZ)
-                                  ? min(ns, ns >= DIRT_RASTER_HZ_DEEP_N ? DIRT_RASTER_HZ_DEEP : DIRT_RASTER_HZ_MIN)
-                                  : ns;
+                    int seg = kNoDepth ? ns : min(ns, ns >= DIRT_RASTER_HZ_DEEP_N ? DIRT_RASTER_HZ_DEEP : DIRT_RASTER_HZ_MIN);
                     int rp = seg;  // first list position not yet run or culled
                     for (;;) {
                         u32x2 oo = *(lds_u32x2 *)&t_wl[wave][base];
@@ -823,8 +797,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                             raster_entry<kNoDepth, false>(qa, frame_recs, pix, pxy, pi, pj, best);
                             raster_entry<kNoDepth, false>(qb, frame_recs, pix, pxy, pi, pj, best);
                         }
-                        if (kNoDepth || !DIRT_RASTER_HZ || rp >= ns) break;
-#if DIRT_RASTER_HZ
+                        if (kNoDepth || rp >= ns) break;
                         const uint32_t wmax = wave_max_u32((uint32_t)(best >> 32));
                         const int kk = rp + lane;
                         const bool tst = kk < ns;
@@ -836,7 +809,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                         base = rp;
                         seg = __popcll(lm);
                         rp = min(rp + 64, ns);
-#endif
                     }
                     for (int k = 0; k < nl; ++k)
                         raster_entry<kNoDepth, true>(load_entry(t_ent, (int)t_wl[wave][kWaveList - 1 - k]), frame_recs, pix,
@@ -844,43 +816,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                 } else if (nst > 0) {
                     best += t_ent[lane % nst].key;
                 }
-#else
-                if (!(AB & 1)) {
-                    for (int c0 = 0; c0 < nst; c0 += 64) {
-                        const uint32_t mm = c0 + lane < nst ? t_mask[c0 + lane] : 0u;
-                        uint64_t mine = __ballot((mm >> wave) & 1u);
-                        const uint64_t big = __ballot((mm >> 4) & 1u) & mine;
-                        if (big == 0) {
-                            // two entries per iteration: both sets of reads in flight before either test
-                            while (mine) {
-                                const int e0 = c0 + (int)__builtin_ctzll(mine);
-                                mine &= mine - 1;
-                                if (mine) {
-                                    const int e1 = c0 + (int)__builtin_ctzll(mine);
-                                    mine &= mine - 1;
-                                    const EntryRegs qa = load_entry(t_ent, e0), qb = load_entry(t_ent, e1);
-                                    raster_entry<kNoDepth, false>(qa, frame_recs, pix, pxy, pi, pj, best);
-                                    raster_entry<kNoDepth, false>(qb, frame_recs, pix, pxy, pi, pj, best);
-                                } else {
-                                    raster_entry<kNoDepth, false>(load_entry(t_ent, e0), frame_recs, pix, pxy, pi, pj, best);
-                                }
-                            }
-                        } else {
-                            while (mine) {
-                                const int bit = (int)__builtin_ctzll(mine);
-                                mine &= mine - 1;
-                                const EntryRegs q = load_entry(t_ent, c0 + bit);
-                                if ((big >> bit) & 1)
-                                    raster_entry<kNoDepth, true>(q, frame_recs, pix, pxy, pi, pj, best);
-                                else
-                                    raster_entry<kNoDepth, false>(q, frame_recs, pix, pxy, pi, pj, best);
-                            }
-                        }
-                    }
-                } else if (nst > 0) {
-                    best += t_ent[lane % nst].key;
-                }
-#endif
                 // t_ent / t_mask are rewritten by the next round of this chunk; a next chunk rewrites
                 // them only after its own filter barrier, and the last round needs no barrier at all
                 if (from + 256 < n_list) __syncthreads();
@@ -975,7 +910,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     for (int k = 0; k < 3; ++k)
         small_rec = small_rec && (uint32_t)(rp.A[k] + kResolveSmall) < 2u * kResolveSmall &&
                     (uint32_t)(rp.B[k] + kResolveSmall) < 2u * kResolveSmall;
-    const bool resolve_small = DIRT_RASTER_RESOLVE32 && __builtin_amdgcn_ballot_w64(!small_rec) == 0;
+    const bool resolve_small = __builtin_amdgcn_ballot_w64(!small_rec) == 0;
     if (resolve_small) {
         const int32_t dx = i * 256 + 128 - rp.X0, dy = j * 256 + 128 - rp.Y0;
 #pragma unroll
@@ -1089,4 +1024,54 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                                                              resolve_small);
         PHASE_TS(5);
     }
+}
+
+// Everything one raster launch takes, by name.  raster_launch() fills the sizes and the layout; a caller sets the
+// pointers its variant uses and leaves the others null / empty (DeepArgs{}: no automatic deep culling, GbufOut{}: no
+// deferred-shading outputs).
+struct RasterLaunch {
+    hipStream_t stream;
+    int B, H, W, C, V, F;
+    int ntx, ntiles, cshift, nctx, ncoarse;  // Layout
+    int64_t nrec;
+    const float *background = nullptr, *colors = nullptr;
+    const Rec *recs = nullptr;  // (FUSED: written by the workgroup of tile 0)
+    const FaceData *fdata = nullptr;
+    const uint32_t *counts = nullptr;
+    uint32_t *flag = nullptr;
+    const uint2 *bins = nullptr;
+    uint32_t slab = 0;  // entries per (frame, coarse tile) slab of `bins`
+    float *pixels = nullptr;
+    int32_t *gbuffer = nullptr;
+    uint8_t *covbits = nullptr;
+    float *zero_a = nullptr, *zero_b = nullptr;  // gradient accumulators [B,V,4] / [B,V,C] to zero-fill in passing
+    const float *verts = nullptr, *cam = nullptr;
+    int sid = DIRT_SHADER_GOURAUD, tcb = 0;  // run-time shader id; channels of `background` (hill's terrain lookup)
+    GbufOut gbo = GbufOut{};
+    const int32_t *faces = nullptr;         // FUSED
+    const uint32_t *stash_hdr = nullptr;    // NOPIX
+    DeepArgs dga = DeepArgs{};
+    const int32_t *gb_in = nullptr;         // RESOLVE
+};
+
+inline RasterLaunch raster_launch(const Layout &L, int B, int H, int W, int C, int V, int F, hipStream_t stream)
+{
+    RasterLaunch a;
+    a.stream = stream; a.tcb = C;
+    a.B = B; a.H = H; a.W = W; a.C = C; a.V = V; a.F = F;
+    a.ntx = L.ntx; a.ntiles = L.ntiles; a.cshift = L.cshift; a.nctx = L.nctx; a.ncoarse = L.ncoarse; a.nrec = L.nrec;
+    return a;
+}
+
+// The one place that launches raster_kernel, and so the one place that knows its parameter order.
+template <int CC, int AB = 0, int SH = DIRT_SHADER_GOURAUD, bool GB = false, bool FUSED = false, bool NOPIX = false,
+          bool OCC = false, bool RESOLVE = false>
+void launch_raster(const RasterLaunch &a)
+{
+    const dim3 grid((unsigned)a.ntiles, (unsigned)a.B);
+    raster_kernel<CC, AB, SH, GB, FUSED, NOPIX, OCC, RESOLVE><<<grid, dim3(256), 0, a.stream>>>(
+        a.background, a.colors, a.recs, a.fdata, a.counts, a.flag, a.bins, a.slab, a.B, a.H, a.W, a.C, a.V, a.F,
+        tile_grid(a.ntx), a.cshift, a.nctx, a.ncoarse, a.nrec, a.pixels, a.gbuffer, a.covbits, a.zero_a,
+        a.zero_a ? (int64_t)a.B * a.V * 4 : 0, a.zero_b, a.zero_b ? (int64_t)a.B * a.V * a.C : 0, a.verts, a.cam, a.sid,
+        a.tcb, a.gbo, a.faces, a.stash_hdr, a.dga, a.gb_in);
 }

@@ -489,8 +489,7 @@ constexpr int kSetupSmallThreads = DIRT_SETUP_SMALL_THREADS;
 // launch the setup (and binning) of B frames x F faces
 template <int AB = 0>
 void launch_setup(const float *vertices, const int32_t *faces, int B, int H, int W, int V, int F, const Layout &L,
-                  Rec *recs, FaceData *fdata, uint32_t *ccount, uint32_t *flag, uint2 *bins, hipStream_t stream,
-                  float *zero_a = nullptr, int64_t nzero_a = 0, float *zero_b = nullptr, int64_t nzero_b = 0,
+                  const SavedView &sv, const ScratchView &sc, hipStream_t stream, float *zero_a = nullptr, int64_t nzero_a = 0, float *zero_b = nullptr, int64_t nzero_b = 0,
                   const uint32_t *stash_hdr = nullptr)
 {
     const bool small = (int64_t)B * ((F + kBinThreads - 1) / kBinThreads) < kSetupSmallGrid;
@@ -504,10 +503,10 @@ void launch_setup(const float *vertices, const int32_t *faces, int B, int H, int
     const float gx = 32768.0f / (float)W, gy = 32768.0f / (float)H;
     if (small)
         setup_kernel<AB, kSetupSmallThreads><<<grid, dim3(kSetupSmallThreads), 0, stream>>>(
-            vertices, faces, V, F, W, H, L.cshift, L.nctx, L.ncoarse, L.nrec, recs, fdata, ccount, flag, bins, L.slab, B,
-            zf, gx, gy, stash_hdr);
+            vertices, faces, V, F, W, H, L.cshift, L.nctx, L.ncoarse, L.nrec, sv.recs, sv.fdata, sc.ccount, sc.flag, sc.bins,
+            L.slab, B, zf, gx, gy, stash_hdr);
     else
         setup_kernel<AB, kBinThreads><<<grid, dim3(kBinThreads), 0, stream>>>(
-            vertices, faces, V, F, W, H, L.cshift, L.nctx, L.ncoarse, L.nrec, recs, fdata, ccount, flag, bins, L.slab, B,
-            zf, gx, gy, stash_hdr);
+            vertices, faces, V, F, W, H, L.cshift, L.nctx, L.ncoarse, L.nrec, sv.recs, sv.fdata, sc.ccount, sc.flag, sc.bins,
+            L.slab, B, zf, gx, gy, stash_hdr);
 }

@@ -78,6 +78,16 @@ def test_gbuffer_outputs_adversarial_fuzz(seed):
     _gbuffer_scene(*scenes.adversarial_scene(100000 + seed, W=W, H=H, C=C))
 
 
+@pytest.mark.parametrize("C", [7, 5])
+def test_gbuffer_outputs_fused_small_scene_wide(C):
+    """The G-buffer outputs of the fused small-scene forward (12 faces <= kFusedMaxF) with 7 channels and with the
+    generic channel path ("square" and "cube" above are its 1- and 3-channel cases): two 40x24 frames, partial tiles
+    at the right and bottom edges."""
+    _, (px, gb, depth, bary, face) = _gbuffer_scene(
+        *scenes.batch_of(scenes.random_triangles, 2, F=12, W=40, H=24, C=C, radius_px=8.0, seed=80 + C))
+    assert 0 < (face >= 0).sum() < face.size
+
+
 def test_gbuffer_batch_and_gradient_unchanged():
     """The G-buffer variant's pixels carry the same gradient as rasterise_batch's."""
     import dirt_amd

@@ -247,6 +247,25 @@ def test_hill_adversarial_fuzz(seed):
     np.testing.assert_array_equal(px, rpx)
 
 
+@pytest.mark.parametrize("sid", [1, 2, 7], ids=["oceanic_horizon", "oceanic", "hill"])
+def test_programs_with_seven_channels(sid):
+    """The 7-channel specialisation of the three procedural instantiations (the other tests here use 1, 3 and 4
+    channels): two 40x24 frames of 40 faces, partial tiles at the right and bottom edges."""
+    bg, v, c, f = scenes.batch_of(scenes.random_triangles, 2, F=40, W=40, H=24, C=7, radius_px=8.0, seed=70)
+    if sid == 7:
+        T = np.stack([scenes.hill_terrain(24, 40, 4)] * 2)
+        cam = hill_cam(HILL_CAMS["harness"])
+        px, gb = _hill_gpu(T, v, f, 7, cam)
+        rpx, rgb, _ = oracle.hill_fwd(T, v, f, 7, cam)
+    else:
+        cam = np.array(list(CAMS["square_test"]) + [0.3, 0.05, 0.5, 0.0, -0.4, 0.01, 0.0, 0.02], np.float32)
+        px, gb = _family_fwd(sid, bg, v, c, f, cam=cam)
+        rpx, rgb, _ = oracle.rasterise_fwd(bg, v, c, f, shader_id=sid, camera_pos=cam)
+    assert 0 < (rgb >= 0).sum() < rgb.size
+    np.testing.assert_array_equal(gb, rgb)
+    np.testing.assert_array_equal(px, rpx)
+
+
 @pytest.mark.parametrize("sid", [1, 2, 3, 4, 5, 6])
 def test_programs_on_narrow_and_odd_frames(sid):
     """Every depth-tested fragment program on frames one tile column wide and on odd sizes (the tile-row

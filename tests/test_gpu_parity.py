@@ -432,6 +432,27 @@ def test_deep_cull_flag_bit_exact(scene):
         assert_close_grad(gv, rgv, "grad_vertices")
 
 
+@pytest.mark.parametrize("C", [1, 7, 5])
+def test_deep_cull_flag_other_channel_classes(C):
+    """DIRT_FWD_DEEP_CULL at the channel specialisations the tests above (C = 3) do not reach -- 1, 7 and the
+    generic one: two 40x24 frames (partial tiles at the
+    right and bottom edges) of 40 faces larger than the frame, so the per-wave lists are long enough for the
+    occluder pass.  Bit-exact g-buffer and pixels, gradients in tolerance."""
+    from dirt_amd.session import RasteriseSession
+    bg, v, c, f = scenes.batch_of(scenes.random_triangles, 2, F=40, W=40, H=24, C=C, radius_px=40.0, seed=50 + C)
+    g = np.random.default_rng(C).standard_normal(bg.shape).astype(np.float32)
+    sess = RasteriseSession(*bg.shape, v.shape[1], f.shape[1], device="cuda", deep_cull=True)
+    sess.forward(*(_gpu(a) for a in (bg, v, c, f)))
+    gbg, gv, gc = (t.cpu().numpy() for t in sess.backward(_gpu(g)))
+    px, gb, _ = oracle.rasterise_fwd(bg, v, c, f)
+    rgv, rgc, rgbg = oracle.rasterise_bwd(v, c, f, px, g, gb)
+    np.testing.assert_array_equal(sess.gbuffer.cpu().numpy(), gb)
+    np.testing.assert_array_equal(sess.pixels.cpu().numpy(), px)
+    np.testing.assert_array_equal(gbg, rgbg)
+    assert_close_grad(gc, rgc, "grad_vertex_colors")
+    assert_close_grad(gv, rgv, "grad_vertices")
+
+
 def test_deep_cull_automatic_rule_through_the_public_op():
     """The public op (dirt_amd.rasterise_batch + autograd, the C++ extension's path) under the automatic deep-cull
     rule: a batch of two deep frames rendered repeatedly -- the later calls take the occluder-culling raster -- with

@@ -181,6 +181,38 @@ def test_recompute_abi_flags_accumulate_and_clean_workspace():
     assert rc == _lib.DIRT_EINVAL and b"workspace" in lib.dirt_last_error()
 
 
+@pytest.mark.parametrize("F,C", [(40, 1), (40, 7), (40, 5), (12, 1), (12, 3), (12, 7), (12, 5)])
+def test_recompute_on_a_miss_every_channel_class(F, C):
+    """The coverage-only raster (NOPIX) doing its work: dirt_rasterise_bwd_recompute on a workspace that holds no
+    stash, so setup + bins + coverage pass run (F = 40) or the fused coverage pass alone (F = 12 <= kFusedMaxF), at
+    each channel specialisation (1, 3, 7, generic; binned with 3 channels is the first call of
+    test_recompute_abi_flags_accumulate_and_clean_workspace).  Two 40x24 frames: partial tiles at the right and
+    bottom edges.  (The single-output op's own backward always finds its forward's stash, where the pass exits at
+    once.)"""
+    from dirt_amd import _lib
+    lib = _lib.load()
+    bg, v, c, f = scenes.batch_of(scenes.random_triangles, 2, F=F, W=40, H=24, C=C, radius_px=8.0, seed=60 + C)
+    B, H, W, _ = bg.shape
+    V = v.shape[1]
+    px, gb, _ = oracle.rasterise_fwd(bg, v, c, f)
+    assert 0 < (gb >= 0).sum() < gb.size
+    gp = np.random.default_rng(F + C).standard_normal(bg.shape).astype(np.float32)
+    rgv, rgc, rgbg = oracle.rasterise_bwd(v, c, f, px, gp, gb)
+    t = [_gpu(a) for a in (bg, v, c, f, px, gp)]
+    n = _lib.recompute_workspace_size(B, H, W, C, V, F)
+    ws = torch.zeros((n,), dtype=torch.uint8, device="cuda")
+    gv, gc = torch.full((B, V, 4), 7.0, device="cuda"), torch.full((B, V, C), 7.0, device="cuda")
+    gbg = torch.empty((B, H, W, C), device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    _lib.check(lib.dirt_rasterise_bwd_recompute(*(x.data_ptr() for x in t), B, H, W, C, V, F, gv.data_ptr(),
+                                                gc.data_ptr(), gbg.data_ptr(), ws.data_ptr(), n,
+                                                _lib.BWD_SCRATCH_CLEAN, stream))
+    assert _lib.stash_state(B, H, W, C, V, F, ws.data_ptr(), n, stream)["last_missed"] == 1
+    np.testing.assert_array_equal(gbg.cpu().numpy(), rgbg)
+    assert_close_grad(gc.cpu().numpy(), rgc, "grad_vertex_colors")
+    assert_close_grad(gv.cpu().numpy(), rgv, "grad_vertices")
+
+
 def test_gradient_stash_hits_misses_and_stays_exact():
     """VERDICT r4 item 3, ABI v11: dirt_rasterise_fwd_stash leaves the forward's records / g-buffer / coverage bits
     in the recompute workspace with a bitwise record of the geometry; dirt_rasterise_bwd_recompute on the same
