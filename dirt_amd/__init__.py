@@ -5,4 +5,4 @@ The reference package re-exports its op wrappers at top level (dirt/__init__.py:
 from .rasterise_ops import *  # noqa: F401,F403
 from .rasterise_ops import __all__  # noqa: F401
 from . import rasterise_ops  # noqa: F401
-from . import lighting, matrices  # noqa: F401,E402
+from . import deferred, lighting, matrices  # noqa: F401,E402

@@ -68,6 +68,11 @@ SIGNATURES = {
     "dirt_diffuse_point_bwd": (_I, [_P, _P, _P, _I64, _P, _P, _I, _P, _P, _P, _P, _P]),
     "dirt_specular_directional_fwd": (_I, [_P, _P, _P, _I64, _P, _P, _P, ctypes.c_float, _I, _P, _P]),
     "dirt_specular_directional_bwd": (_I, [_P, _P, _P, _I64, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P, _P]),
+    "dirt_dilate_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "dirt_dilate_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "dirt_deferred_shade_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
+    "dirt_deferred_shade_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P,
+                                     _P, _P]),
     "dirt_last_error": (ctypes.c_char_p, []),
 }
 

@@ -268,6 +268,7 @@ struct EventPair {
 #include "raster_kernel.h"
 #include "grad_kernel.h"
 #include "lighting_kernels.h"
+#include "deferred_kernels.h"
 
 // zero two float arrays in one launch (the backward's atomically accumulated outputs)
 __global__ __launch_bounds__(256) void zero2_kernel(float *__restrict__ a, int64_t na, float *__restrict__ b, int64_t nb)
@@ -1384,6 +1385,141 @@ int dirt_specular_directional_bwd(const float *positions, const float *normals, 
     specular_bwd_kernel<<<dim3(light_blocks(N)), dim3(kLightThreads), 0, stream>>>(
         positions, normals, reflectivities, N, light_direction, light_color, camera_position, shininess, double_sided,
         grad_out, grad_positions, grad_normals, grad_reflectivities);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- deferred shading: silhouette dilation and the fused G-buffer lighting (deferred_kernels.h)
+
+namespace {
+
+// shared argument checks of the four entry points: DIRT_OK with *pixels = B * H * W (0: nothing to do)
+int deferred_sizes(const char *op, int B, int H, int W, int C, int64_t *pixels)
+{
+    char msg[160];
+    *pixels = 0;
+    if (B < 0) {
+        snprintf(msg, sizeof(msg), "%s: batch size must be non-negative", op);
+        return fail(DIRT_EINVAL, msg);
+    }
+    if (H < 1 || W < 1 || H > DIRT_MAX_DIM || W > DIRT_MAX_DIM) {
+        snprintf(msg, sizeof(msg), "%s: height, width must be in 1..%d", op, DIRT_MAX_DIM);
+        return fail(DIRT_EINVAL, msg);
+    }
+    if (C < 1 || C > DIRT_MAX_CHANNELS) {
+        snprintf(msg, sizeof(msg), "%s: expects 1 <= channels <= %d", op, DIRT_MAX_CHANNELS);
+        return fail(DIRT_EINVAL, msg);
+    }
+    const int64_t n = (int64_t)B * H * W;
+    if ((n + kLightThreads - 1) / kLightThreads > 0x7fffffffLL) {
+        snprintf(msg, sizeof(msg), "%s: too large (more pixels than one launch covers)", op);
+        return fail(DIRT_EINVAL, msg);
+    }
+    *pixels = n;
+    return DIRT_OK;
+}
+
+template <int C>
+void launch_dilate_fwd(const float *x, const uint8_t *mask, int H, int W, int64_t n, float *out, uint32_t *route,
+                       hipStream_t stream)
+{
+    dilate_fwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(x, mask, H, W, n, out, route);
+}
+
+template <int C>
+void launch_dilate_bwd(const float *grad, const uint32_t *route, int H, int W, int64_t n, float *grad_x,
+                       hipStream_t stream)
+{
+    dilate_bwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(grad, route, H, W, n, grad_x);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_dilate_fwd(const float *x, const uint8_t *mask, int B, int H, int W, int C, float *out, uint32_t *route,
+                    void *stream_)
+{
+    int64_t n;
+    const int rc = deferred_sizes("dilate", B, H, W, C, &n);
+    if (rc || n == 0) return rc;
+    if (!x || !out || !route) return fail(DIRT_EINVAL, "dilate: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    switch (C) {
+    case 1: launch_dilate_fwd<1>(x, mask, H, W, n, out, route, stream); break;
+    case 2: launch_dilate_fwd<2>(x, mask, H, W, n, out, route, stream); break;
+    case 3: launch_dilate_fwd<3>(x, mask, H, W, n, out, route, stream); break;
+    case 4: launch_dilate_fwd<4>(x, mask, H, W, n, out, route, stream); break;
+    case 5: launch_dilate_fwd<5>(x, mask, H, W, n, out, route, stream); break;
+    case 6: launch_dilate_fwd<6>(x, mask, H, W, n, out, route, stream); break;
+    case 7: launch_dilate_fwd<7>(x, mask, H, W, n, out, route, stream); break;
+    default: launch_dilate_fwd<8>(x, mask, H, W, n, out, route, stream); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_dilate_bwd(const float *grad_out, const uint32_t *route, int B, int H, int W, int C, float *grad_x,
+                    void *stream_)
+{
+    int64_t n;
+    const int rc = deferred_sizes("dilate", B, H, W, C, &n);
+    if (rc || n == 0) return rc;
+    if (!grad_out || !route || !grad_x) return fail(DIRT_EINVAL, "dilate: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    switch (C) {
+    case 1: launch_dilate_bwd<1>(grad_out, route, H, W, n, grad_x, stream); break;
+    case 2: launch_dilate_bwd<2>(grad_out, route, H, W, n, grad_x, stream); break;
+    case 3: launch_dilate_bwd<3>(grad_out, route, H, W, n, grad_x, stream); break;
+    case 4: launch_dilate_bwd<4>(grad_out, route, H, W, n, grad_x, stream); break;
+    case 5: launch_dilate_bwd<5>(grad_out, route, H, W, n, grad_x, stream); break;
+    case 6: launch_dilate_bwd<6>(grad_out, route, H, W, n, grad_x, stream); break;
+    case 7: launch_dilate_bwd<7>(grad_out, route, H, W, n, grad_x, stream); break;
+    default: launch_dilate_bwd<8>(grad_out, route, H, W, n, grad_x, stream); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_fwd(const float *positions, const float *colors, const float *normals, int B, int H, int W,
+                            const float *ambient_color, const float *light_direction, const float *diffuse_color,
+                            const float *specular_color, const float *camera_position, float shininess,
+                            int double_sided, float *pixels, uint8_t *valid, uint32_t *route, void *stream_)
+{
+    int64_t n;
+    const int rc = deferred_sizes("deferred_shade", B, H, W, 3, &n);
+    if (rc || n == 0) return rc;
+    if (!positions || !colors || !normals || !ambient_color || !light_direction || !diffuse_color || !specular_color ||
+        !camera_position || !pixels || !valid || !route)
+        return fail(DIRT_EINVAL, "deferred_shade: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeLights L = {ambient_color, light_direction, diffuse_color, specular_color, camera_position, shininess,
+                           double_sided};
+    deferred_shade_fwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        positions, colors, normals, H, W, n, L, pixels, valid, route);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_bwd(const float *positions, const float *colors, const float *normals, int B, int H, int W,
+                            const float *ambient_color, const float *light_direction, const float *diffuse_color,
+                            const float *specular_color, const float *camera_position, float shininess,
+                            int double_sided, const float *grad_pixels, const uint32_t *route, float *grad_positions,
+                            float *grad_colors, float *grad_normals, void *stream_)
+{
+    int64_t n;
+    const int rc = deferred_sizes("deferred_shade", B, H, W, 3, &n);
+    if (rc || n == 0 || (!grad_positions && !grad_colors && !grad_normals)) return rc;
+    if (!positions || !colors || !normals || !ambient_color || !light_direction || !diffuse_color || !specular_color ||
+        !camera_position || !grad_pixels || !route)
+        return fail(DIRT_EINVAL, "deferred_shade: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeLights L = {ambient_color, light_direction, diffuse_color, specular_color, camera_position, shininess,
+                           double_sided};
+    deferred_shade_bwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        positions, colors, normals, H, W, n, L, grad_pixels, route, grad_positions, grad_colors, grad_normals);
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }

@@ -76,7 +76,8 @@ extern "C" {
  * dirt_diffuse_directional_*, dirt_specular_directional_*, dirt_diffuse_point_*; 10: + dirt_stream_capture_id;
  * 11: + dirt_rasterise_fwd_stash, the recompute workspace grows by the gradient stash; 12: the Gouraud forward
  * picks the occluder culling by itself (DIRT_FWD_DEEP_CULL forces it, + DIRT_FWD_DEEP_CULL_OFF); 13: +
- * dirt_rasterise_fwd_resolve) */
+ * dirt_rasterise_fwd_resolve; added at 13 without a bump, no signature or layout changed: dirt_dilate_fwd,
+ * dirt_dilate_bwd, dirt_deferred_shade_fwd, dirt_deferred_shade_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -280,6 +281,43 @@ int dirt_specular_directional_bwd(const float *positions, const float *normals, 
                                   const float *camera_position, float shininess, int double_sided,
                                   const float *grad_out, float *grad_positions, float *grad_normals,
                                   float *grad_reflectivities, void *stream);
+
+/* Deferred shading in pixel space (samples/deferred.py:85-115): silhouette dilation and the fused G-buffer lighting.
+ * One launch per call; the backwards are gathers in a fixed order (no float atomics), so their gradients are
+ * bit-identical from run to run.  H, W in 1..DIRT_MAX_DIM, C in 1..DIRT_MAX_CHANNELS, B >= 0 (B == 0: no-op).
+ *
+ * dilate: x, out [B,H,W,C]; mask [B,H,W] uint8, NULL = "any channel of x[p] is +inf or -inf".
+ *   out[p,c] = mask[p] ? max of x[.,c] over the 3x3 window around p clipped to its frame : x[p,c]
+ * The max scans the window in row-major order from its first element and replaces the running value when
+ * v > m || isnan(v) (the framework's CPU max_pool2d): the first maximum wins ties, a NaN in the window gives NaN
+ * (the last one wins), an all -inf window picks its first element.  route [B,H,W] receives a 4-bit code per channel
+ * from bit 0: 0..8 = the winner's window position (dy + 1) * 3 + (dx + 1), 15 = not dilated (unused nibbles 0).
+ * Backward, from grad_out and route alone:
+ *   grad_x[p,c] = (code(p,c) == 15 ? grad_out[p,c] : 0) + the grad_out[q,c] of the window positions q around p, in
+ *   row-major order and including p itself, whose code for c points back at p.
+ * out / grad_x must not alias x / grad_out. */
+int dirt_dilate_fwd(const float *x, const uint8_t *mask, int B, int H, int W, int C, float *out, uint32_t *route,
+                    void *stream);
+int dirt_dilate_bwd(const float *grad_out, const uint32_t *route, int B, int H, int W, int C, float *grad_x,
+                    void *stream);
+/* deferred_shade: positions, colors, normals, pixels [B,H,W,3]; the five light parameters are DEVICE pointers to 3
+ * floats (no gradient with respect to them).  Per pixel: bg = any channel of positions[p] is +-inf; positions and
+ * normals are dilated as above, both under bg; valid = all six dilated values are finite;
+ *   pixels = valid ? (diffuse_directional(normals_d, colors) + specular_directional(positions_d, normals_d, colors))
+ *                    + colors * ambient_color : 0
+ * (both lights one direction, the fused lighting helpers' arithmetic).  valid [B,H,W] uint8; route [B,H,W]: the
+ * positions' codes in bits 0..11, the normals' in bits 12..23, valid in bit 31.
+ * Backward: grad_positions / grad_colors / grad_normals [B,H,W,3], each fully overwritten, each may be NULL; the
+ * lighting adjoints (zero at invalid pixels) routed through the dilation by the gather above. */
+int dirt_deferred_shade_fwd(const float *positions, const float *colors, const float *normals, int B, int H, int W,
+                            const float *ambient_color, const float *light_direction, const float *diffuse_color,
+                            const float *specular_color, const float *camera_position, float shininess,
+                            int double_sided, float *pixels, uint8_t *valid, uint32_t *route, void *stream);
+int dirt_deferred_shade_bwd(const float *positions, const float *colors, const float *normals, int B, int H, int W,
+                            const float *ambient_color, const float *light_direction, const float *diffuse_color,
+                            const float *specular_color, const float *camera_position, float shininess,
+                            int double_sided, const float *grad_pixels, const uint32_t *route, float *grad_positions,
+                            float *grad_colors, float *grad_normals, void *stream);
 
 /* Thread-local message for the last non-OK return on this thread. */
 const char *dirt_last_error(void);

@@ -1,0 +1,431 @@
+"""The fused deferred-shading kernels (dirt_amd/csrc/deferred_kernels.h through dirt_amd.deferred) against the float64
+statement of record (tests/deferred_cases.py) on its table of edge frames.
+
+Dilation: forward and route bit-exact; backward bit-exact for integer cotangents, within 10 * 2^-24 * (sum of the
+absolute routed terms) for float ones (at most 10 terms summed in one fixed order, 2^-24 relative error per
+addition); gradients bit-identical from run to run.
+Shade: valid exact, invalid pixels exactly 0, valid pixels within the lighting contract applied per term and summed
+(3 * FWD_ATOL + FWD_RTOL * (|ambient| + |diffuse| + |specular|)), gradients within GRAD_FRAC of their reference's
+scale (tests/lighting_cases.py).  Each test prints its worst measured ratio of error to bound.
+"""
+import gc
+
+import numpy as np
+import pytest
+import torch
+
+import deferred_cases as dc
+import deferred_pipeline as dp
+import lighting_cases
+from dirt_amd import _lib, deferred
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+NAMES = ("positions", "colors", "normals")
+
+
+def _gpu(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _fused_node(y, cls):
+    """y comes from the fused autograd function `cls` (directly, or through the [0] of an unbatched call)"""
+    assert y.grad_fn is not None
+    names = [y.grad_fn.name()] + [fn.name() for fn, _ in y.grad_fn.next_functions if fn is not None]
+    assert any(cls in n for n in names), names
+
+
+def _raw_dilate(x, mask):
+    """dirt_dilate_fwd itself: (out, route) as numpy"""
+    xt = _gpu(x)
+    mt = None if mask is None else _gpu(mask)
+    B, H, W, C = x.shape
+    out = torch.empty_like(xt)
+    route = torch.empty((B, H, W), dtype=torch.int32, device=DEV)
+    _lib.check(_lib.load().dirt_dilate_fwd(xt.data_ptr(), None if mt is None else mt.data_ptr(), B, H, W, C,
+                                           out.data_ptr(), route.data_ptr(),
+                                           torch.cuda.current_stream(DEV).cuda_stream))
+    torch.cuda.synchronize()
+    return out.cpu().numpy(), route.cpu().numpy().view(np.uint32)
+
+
+def _dilate_grad(x, mask, g):
+    xt = _gpu(x).requires_grad_(True)
+    y = deferred.dilate(xt, None if mask is None else _gpu(mask))
+    _fused_node(y, "_DilateFn")
+    gx, = torch.autograd.grad(y, [xt], _gpu(g))
+    return y.detach().cpu().numpy(), gx.cpu().numpy()
+
+
+def _check_dilate(x, mask, ref, route, tag):
+    out, r = _raw_dilate(x, mask)
+    assert np.array_equal(_bits(out), _bits(ref)), tag
+    assert np.array_equal(r, route), tag
+    rng = np.random.default_rng(7)
+    gi = rng.integers(-3, 4, x.shape).astype(np.float32)
+    y, gx = _dilate_grad(x, mask, gi)
+    assert np.array_equal(_bits(y), _bits(ref)), tag
+    assert np.array_equal(gx.astype(np.float64), dc.dilate_vjp(gi, route)[0]), tag
+    gf = rng.standard_normal(x.shape).astype(np.float32)
+    _, gx1 = _dilate_grad(x, mask, gf)
+    _, gx2 = _dilate_grad(x, mask, gf)
+    assert np.array_equal(_bits(gx1), _bits(gx2)), tag  # a gather in a fixed order: no run-to-run difference
+    want, absum = dc.dilate_vjp(gf, route)
+    assert np.all(np.abs(gx1 - want) <= 10 * 2.0 ** -24 * absum), tag
+
+
+@pytest.mark.parametrize("explicit", [False, True], ids=["derived", "explicit"])
+@pytest.mark.parametrize("ident", dc.FRAME_IDS)
+def test_dilate_matches_the_statement(ident, explicit):
+    for C in (1, 3, 8):
+        for values in ("random", "ties"):
+            x, mask, ref, route = dc.dilate_case(ident, C, values, explicit)
+            _check_dilate(x, mask, ref, route, (ident, C, values))
+
+
+@pytest.mark.parametrize("C", [1, 3, 8])
+def test_dilate_special_windows(C):
+    """Windows holding +inf, one NaN, two NaNs (NaN out, the last one routed), all -inf (the first element), and a
+    constant plateau (the first maximum)."""
+    x, mask = dc.special_windows(C)
+    ref, route = dc.dilate(x, mask)
+    assert np.isnan(ref[0, 10, 4]).all() and (dc.codes(route, C)[0, 10, 4] == 5).all()
+    _check_dilate(x, mask, ref, route, C)
+
+
+def test_dilate_offsets_past_2_31():
+    """B * H * W * C = 17 * 4096 * 4096 * 8 = 2.28e9 elements: the element offsets of the last frame do not fit a
+    signed 32-bit index.  Background probes at frame corners, in the middle and at the very end, forward and backward
+    against the statement on each probe's window; nothing else in the tensors changes.  Two 9.1 GB tensors are alive
+    at a time (no full-size temporaries: the comparisons go frame by frame), and the allocator's blocks are released
+    at the end."""
+    B, H, W, C = 17, 4096, 4096, 8
+    assert B * H * W * C > 2 ** 31
+    lib, stream = _lib.load(), torch.cuda.current_stream(DEV).cuda_stream
+    rng = np.random.default_rng(11)
+    probes = [(B - 1, H - 4, W - 4), (B - 1, H - 1, W - 1), (B - 1, 0, 0), (0, 0, W - 1), (8, 2048, 2049)]
+    try:
+        x = torch.zeros((B, H, W, C), device=DEV)
+        windows = []
+        for b, y, x0 in probes:
+            ys, xs = slice(max(y - 1, 0), min(y + 2, H)), slice(max(x0 - 1, 0), min(x0 + 2, W))
+            patch = rng.integers(1, 5, (ys.stop - ys.start, xs.stop - xs.start, C)).astype(np.float32)  # with ties
+            patch[y - ys.start, x0 - xs.start] = -np.inf
+            x[b, ys, xs] = _gpu(patch)
+            windows.append((b, ys, xs, (y - ys.start, x0 - xs.start), patch))
+        out = torch.empty_like(x)
+        route = torch.empty((B, H, W), dtype=torch.int32, device=DEV)
+        _lib.check(lib.dirt_dilate_fwd(x.data_ptr(), None, B, H, W, C, out.data_ptr(), route.data_ptr(), stream))
+        own = int(np.int32(np.uint32(sum(15 << (4 * c) for c in range(C)))))
+        assert sum(int((out[b] != x[b]).sum()) for b in range(B)) == C * len(probes)
+        assert sum(int((route[b] != own).sum()) for b in range(B)) == len(probes)
+        refs = []
+        for b, ys, xs, at, patch in windows:
+            ref, ref_route = dc.dilate(patch)
+            assert np.array_equal(_bits(out[b, ys, xs].cpu().numpy()), _bits(ref))
+            assert np.array_equal(route[b, ys, xs].cpu().numpy().view(np.uint32), ref_route)
+            refs.append(ref_route)
+        del x, out
+        g = torch.zeros((B, H, W, C), device=DEV)
+        grads = []
+        for b, ys, xs, at, patch in windows:
+            gp = np.zeros(patch.shape, np.float32)
+            gp[at] = rng.integers(1, 4, C)
+            g[b, ys, xs] = _gpu(gp)
+            grads.append(gp)
+        gx = torch.empty_like(g)
+        _lib.check(lib.dirt_dilate_bwd(g.data_ptr(), route.data_ptr(), B, H, W, C, gx.data_ptr(), stream))
+        nonzero = 0
+        for (b, ys, xs, at, patch), ref_route, gp in zip(windows, refs, grads):
+            want = dc.dilate_vjp(gp, ref_route)[0]
+            assert np.array_equal(gx[b, ys, xs].cpu().numpy().astype(np.float64), want)
+            nonzero += int(np.count_nonzero(want))
+        assert nonzero == C * len(probes)
+        assert sum(int(torch.count_nonzero(gx[b])) for b in range(B)) == nonzero
+    finally:
+        x = out = g = gx = route = None
+        gc.collect()
+        torch.cuda.empty_cache()
+
+
+def test_dilate_forms():
+    """[H,W,C] and non-contiguous inputs, bool and integer masks; float64 and DIRT_FUSED_DEFERRED=0 take the statement."""
+    x, mask, ref, _ = dc.dilate_case("15x17-checkerboard", 3, "random", True)
+    xt = _gpu(x)
+    y = deferred.dilate(xt[0].requires_grad_(True), _gpu(mask)[0].bool())
+    _fused_node(y, "_DilateFn")
+    assert y.shape == x.shape[1:] and np.array_equal(_bits(y.detach().cpu().numpy()), _bits(ref[0]))
+    wide = torch.zeros((1, 15, 17, 6), device=DEV)
+    wide[..., ::2] = xt
+    y = deferred.dilate(wide[..., ::2], _gpu(mask).long())
+    assert np.array_equal(_bits(y.cpu().numpy()), _bits(ref))
+    y64 = deferred.dilate(xt.double().requires_grad_(True), _gpu(mask))
+    assert "_DilateFn" not in y64.grad_fn.name()
+    assert np.array_equal(y64.detach().cpu().numpy(), ref.astype(np.float64))
+
+
+# ---- shade
+
+def _lights(L):
+    return [_gpu(v) for v in L.vectors()]
+
+
+def _shade_gpu(inputs, L, grad, needs=(True, True, True), lights=None):
+    ts = [_gpu(a).requires_grad_(need) for a, need in zip(inputs, needs)]
+    pixels, valid = deferred.shade(*ts, *(lights or _lights(L)), L.shininess, L.double_sided)
+    if any(needs):
+        pixels.backward(_gpu(grad))
+    torch.cuda.synchronize()
+    return pixels, valid, [None if t.grad is None else t.grad.cpu().numpy() for t in ts]
+
+
+def _check_shade(got, ref, vjp, tag, names=NAMES):
+    """-> worst ratios (forward, gradients) of error to bound"""
+    pixels, valid, grads = got
+    pixels, valid = pixels.detach().cpu().numpy(), valid.cpu().numpy()
+    assert valid.dtype == np.bool_ and valid.shape == ref["valid"].shape + (1,), tag
+    assert np.array_equal(valid[..., 0], ref["valid"]), tag
+    v = ref["valid"]
+    assert np.array_equal(pixels[~v], np.zeros_like(pixels[~v])), tag
+    err, bound = np.abs(pixels - ref["pixels"])[v], dc.shade_fwd_bound(ref)[v]
+    fwd = float((err / bound).max()) if err.size else 0.0
+    assert fwd <= 1.0, (tag, fwd)
+    worst = 0.0
+    for name, g in zip(NAMES, grads):
+        if name in names:
+            r = lighting_cases.grad_ratio(g, vjp[name], "%s d %s" % (tag, name))
+            assert r <= 1.0, (tag, name, r)
+            worst = max(worst, r)
+    print("shade %s: forward %.3f of its bound, gradients %.3f of theirs" % (tag, fwd, worst))
+    return fwd, worst
+
+
+@pytest.mark.parametrize("ident", dc.FRAME_IDS)
+def test_shade_matches_the_statement(ident):
+    inputs, L, ref, grad, vjp = dc.shade_case(ident)
+    ts = [_gpu(a).requires_grad_(True) for a in inputs]
+    pixels, valid = deferred.shade(*ts, *_lights(L), L.shininess, L.double_sided)
+    _fused_node(pixels, "_ShadeFn")
+    assert not valid.requires_grad
+    grads = torch.autograd.grad(pixels, ts, _gpu(grad))
+    _check_shade((pixels, valid, [g.cpu().numpy() for g in grads]), ref, vjp, ident)
+    again = torch.autograd.grad(deferred.shade(*ts, *_lights(L), L.shininess, L.double_sided)[0], ts, _gpu(grad))
+    for a, b in zip(grads, again):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))  # bit-identical from run to run
+
+
+@pytest.mark.parametrize("shininess", [0, 1, 6, 2.5])
+@pytest.mark.parametrize("two", [False, True], ids=["one_sided", "double_sided"])
+def test_shade_options(two, shininess):
+    for ident in ("15x17-checkerboard", "63x65-hole", "3x5x6-leak"):
+        inputs, L, ref, grad, vjp = dc.shade_case(ident, shininess, two)
+        _check_shade(_shade_gpu(inputs, L, grad), ref, vjp, "%s two=%d k=%g" % (ident, two, shininess))
+
+
+@pytest.mark.parametrize("needs", [(a, b, c) for a in (False, True) for b in (False, True) for c in (False, True)],
+                         ids=lambda n: "".join(ch for ch, on in zip("pcn", n) if on) or "none")
+def test_shade_gradient_subsets(needs):
+    """Every subset of {positions, colors, normals} requiring a gradient: the requested ones as the statement's (and
+    bit-identical to the all-three run's), the others None."""
+    inputs, L, ref, grad, vjp = dc.shade_case("15x17-block_br")
+    got = _shade_gpu(inputs, L, grad, needs)
+    full = _shade_gpu(inputs, L, grad)
+    _check_shade(got, ref, vjp, "subset %s" % (needs,), [n for n, need in zip(NAMES, needs) if need])
+    for g, f, need in zip(got[2], full[2], needs):
+        assert (g is not None) == need
+        if need:
+            assert np.array_equal(_bits(g), _bits(f))
+    assert (got[0].grad_fn is not None) == any(needs)
+
+
+def test_shade_nan_normal_invalidates_only_its_reach():
+    """A NaN normal at a covered pixel on the silhouette: that pixel and the background neighbours whose window holds
+    it are invalid (exactly 0, no gradient); every output and gradient stays finite and as the statement's; pixels
+    out of its reach are bit-identical to the run without it."""
+    ident = "15x17-block_tl"  # covered rows 0..7, columns 0..8
+    clean, L, _, grad, _ = dc.shade_case(ident)
+    pos, col, nrm = (a.copy() for a in clean)
+    nrm[0, 7, 8, 1] = np.nan
+    ref, vjp = dc.shade(pos, col, nrm, L), dc.shade_vjp(pos, col, nrm, L, grad)
+    for y, x0 in ((7, 8), (8, 7), (8, 8), (8, 9), (7, 9), (6, 9)):
+        assert not ref["valid"][0, y, x0]
+    assert ref["valid"][0, 6, 8] and ref["valid"][0, 5, 9]
+    got = _shade_gpu((pos, col, nrm), L, grad)
+    _check_shade(got, ref, vjp, "nan normal")
+    assert all(np.all(np.isfinite(g)) for g in got[2]) and bool(torch.isfinite(got[0]).all())
+    base = _shade_gpu(clean, L, grad)
+    yy, xx = np.mgrid[0:15, 0:17]
+    far_px = np.maximum(np.abs(yy - 7), np.abs(xx - 8)) > 1   # outputs: the pixel and its eight neighbours
+    far_gr = np.maximum(np.abs(yy - 7), np.abs(xx - 8)) > 2   # gradients: what those nine route to
+    assert np.array_equal(_bits(got[0].detach().cpu().numpy())[0][far_px], _bits(base[0].detach().cpu().numpy())[0][far_px])
+    assert np.array_equal(got[1].cpu().numpy()[0][far_px], base[1].cpu().numpy()[0][far_px])
+    for g, b in zip(got[2], base[2]):
+        assert np.array_equal(_bits(g)[0][far_gr], _bits(b)[0][far_gr])
+
+
+def test_shade_dilates_normals_under_the_positions_mask():
+    """The two G-buffers' backgrounds disagree: a normal at -inf where the position is finite is not dilated (the
+    pixel is invalid), a finite normal where the position is -inf is replaced by its window's maximum."""
+    clean, L, _, grad, _ = dc.shade_case("15x17-checkerboard")
+    pos, col, nrm = (a.copy() for a in clean)
+    covered = np.isfinite(pos).all(-1)
+    assert covered[0, 4, 4] and covered[0, 8, 10] and not covered[0, 4, 5] and not covered[0, 9, 10]
+    nrm[0, 4, 4] = -np.inf
+    nrm[0, 8, 10, 2] = -np.inf
+    nrm[0, 4, 5] = (0.0, 0.6, 0.8)
+    nrm[0, 9, 10] = (10.0, 10.0, 10.0)
+    ref, vjp = dc.shade(pos, col, nrm, L), dc.shade_vjp(pos, col, nrm, L, grad)
+    assert not ref["valid"][0, 4, 4] and not ref["valid"][0, 8, 10] and ref["valid"][0, 9, 10]
+    _check_shade(_shade_gpu((pos, col, nrm), L, grad), ref, vjp, "mismatched backgrounds")
+
+
+def test_shade_forms():
+    """[H,W,3] and non-contiguous inputs run the fused kernels and give the batched, contiguous result."""
+    inputs, L, ref, grad, vjp = dc.shade_case("15x17-island")
+    base = _shade_gpu(inputs, L, grad)
+    got = _shade_gpu([a[0] for a in inputs], L, grad[0])
+    assert got[0].shape == (15, 17, 3) and got[1].shape == (15, 17, 1)
+    _fused_node(got[0], "_ShadeFn")
+    assert np.array_equal(_bits(got[0].detach().cpu().numpy()), _bits(base[0].detach().cpu().numpy())[0])
+    for g, b in zip(got[2], base[2]):
+        assert np.array_equal(_bits(g), _bits(b)[0])
+    wide = [torch.zeros((1, 15, 17, 6), device=DEV) for _ in inputs]
+    for w, a in zip(wide, inputs):
+        w[..., ::2] = _gpu(a)
+    ts = [w.requires_grad_(True) for w in wide]
+    views = [t[..., ::2] for t in ts]
+    assert not views[0].is_contiguous()
+    pixels, valid = deferred.shade(*views, *_lights(L), L.shininess, L.double_sided)
+    _fused_node(pixels, "_ShadeFn")
+    pixels.backward(_gpu(grad).expand_as(pixels))
+    assert torch.equal(pixels.detach(), base[0].detach()) and torch.equal(valid, base[1])
+    for t, b in zip(ts, base[2]):
+        assert np.array_equal(_bits(t.grad.cpu().numpy()[..., ::2]), _bits(b))
+        assert float(t.grad[..., 1::2].abs().max()) == 0.0
+
+
+def test_shade_routes_what_the_kernels_do_not_take(monkeypatch):
+    """A light parameter that needs a gradient, float64 tensors and DIRT_FUSED_DEFERRED=0 run the framework-op
+    statement: no fused node, the statement's values, and the light's gradient exists."""
+    inputs, L, ref, grad, vjp = dc.shade_case("15x17-hole")
+
+    def check(pixels, valid, tol):
+        assert "_ShadeFn" not in pixels.grad_fn.name()
+        assert np.array_equal(valid.cpu().numpy()[..., 0], ref["valid"])
+        assert np.all(np.abs(pixels.detach().cpu().numpy() - ref["pixels"]) <= tol)
+
+    ts = [_gpu(a).requires_grad_(True) for a in inputs]
+    lights = _lights(L)
+    lights[1].requires_grad_(True)
+    pixels, valid = deferred.shade(*ts, *lights, L.shininess, L.double_sided)
+    check(pixels, valid, dc.shade_fwd_bound(ref))
+    gl, = torch.autograd.grad((pixels * _gpu(grad)).sum(), [lights[1]])
+    assert bool(torch.isfinite(gl).all()) and float(gl.abs().sum()) > 0
+    t64 = [_gpu(a).double().requires_grad_(True) for a in inputs]
+    pixels, valid = deferred.shade(*t64, *[v.double() for v in _lights(L)], L.shininess, L.double_sided)
+    check(pixels, valid, 1e-12)
+    g64 = torch.autograd.grad(pixels, t64, _gpu(grad).double())
+    for name, g in zip(NAMES, g64):
+        assert np.abs(g.cpu().numpy() - vjp[name]).max() <= 1e-12 * max(1.0, np.abs(vjp[name]).max()), name
+    monkeypatch.setattr(deferred, "_FUSED_ENABLED", False)
+    pixels, valid = deferred.shade(*ts, *_lights(L), L.shininess, L.double_sided)
+    check(pixels, valid, dc.shade_fwd_bound(ref))
+    y = deferred.dilate(ts[0])
+    assert "_DilateFn" not in y.grad_fn.name()
+
+
+def test_fused_backward_refuses_double_backward(monkeypatch):
+    inputs, L, ref, grad, vjp = dc.shade_case("15x17-hole")
+    ts = [_gpu(a).requires_grad_(True) for a in inputs]
+    pixels, _ = deferred.shade(*ts, *_lights(L), L.shininess, L.double_sided)
+    with pytest.raises(RuntimeError, match="create_graph"):
+        torch.autograd.grad(torch.where(_gpu(ref["valid"])[..., None], pixels, 0.0).square().sum(), [ts[1]],
+                            create_graph=True)
+    y = deferred.dilate(ts[1])
+    with pytest.raises(RuntimeError, match="create_graph"):
+        torch.autograd.grad(y.square().sum(), [ts[1]], create_graph=True)
+    monkeypatch.setattr(deferred, "_FUSED_ENABLED", False)
+    pixels, _ = deferred.shade(*ts, *_lights(L), L.shininess, L.double_sided)
+    gc_, = torch.autograd.grad(pixels.square().sum(), [ts[1]], create_graph=True)
+    gg, = torch.autograd.grad(gc_.sum(), [ts[2]])
+    assert bool(torch.isfinite(gg).all())
+
+
+def test_shade_captures_into_a_graph():
+    """One forward and backward captured with torch.cuda.graph (the pattern of INTEGRATION.md section 5: no eager
+    autograd graph alive at the capture), replayed after the inputs changed in place: equal to the eager result."""
+    first, L, _, grad, _ = dc.shade_case("63x65-block_tl")
+    second = dc.shade_case("63x65-checkerboard")[0]
+    ts = [_gpu(a).requires_grad_(True) for a in first]
+    lights, g = _lights(L), _gpu(grad)
+    out = {}
+
+    def step():
+        pixels, valid = deferred.shade(*ts, *lights, L.shininess, L.double_sided)
+        out["pixels"], out["valid"] = pixels, valid
+        out["grads"] = torch.autograd.grad(pixels, ts, g)
+
+    gc.collect()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    out.clear()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    with torch.no_grad():
+        for t, a in zip(ts, second):
+            t.copy_(_gpu(a))
+    graph.replay()
+    torch.cuda.synchronize()
+    got = (out["pixels"].detach().clone(), out["valid"].clone(), [x.clone() for x in out["grads"]])
+    del graph
+    out.clear()
+    eager = _shade_gpu(second, L, grad)
+    assert torch.equal(got[0], eager[0].detach()) and torch.equal(got[1], eager[1])
+    for a, b in zip(got[2], eager[2]):
+        assert np.array_equal(_bits(a.cpu().numpy()), _bits(b))
+
+
+def test_chain_with_the_fused_shade_against_the_pipeline_glue():
+    """The deferred chain at 64 x 64 over dp.grid_surface(n=12): one set of G-buffers shaded by deferred.shade and by
+    tests/deferred_pipeline.py::shade, both on the GPU.  valid equal; pixels within the contract of the statement and of
+    the glue alike; d loss / d world vertices within
+    1e-2 in relative L2 norm (the tolerance of test_config4_chain_all_on_gpu_against_oracle_chain for it).
+    Measured on an MI355X: pixels 0.005 of the bound against the statement and identical to the glue's (the same
+    arithmetic in the same order), gradient 7.6e-8 in relative L2 (the rasteriser's float atomics)."""
+    H = W = 64
+    world, faces, albedo = dp.grid_surface(n=12)
+    Vw = _gpu(world).requires_grad_(True)
+    f, al = _gpu(faces), _gpu(albedo)
+    wts = torch.rand((H, W, 3), device=DEV, generator=torch.Generator(device=DEV).manual_seed(3))
+    pos, col, nrm, _ = dp.gbuffers(dp.hip_render, Vw, f, al, H, W)
+    grey, ld, red, white = dp._constants(DEV)
+    cam = dp.camera_position(H, W, DEV)
+    pf, vf = deferred.shade(pos, col, nrm, grey, ld, red, white, cam, 6., False)
+    _fused_node(pf, "_ShadeFn")
+    pg, vg = dp.shade(pos, col, nrm, H, W)
+    assert torch.equal(vf, vg) and bool(vf.any()) and not bool(vf.all())
+    L = dc.Lights(camera=cam.cpu().numpy())
+    L.ambient, L.direction, L.diffuse, L.specular = (t.cpu().numpy() for t in (grey, ld, red, white))
+    ref = dc.shade(*(t.detach().cpu().numpy() for t in (pos, col, nrm)), L)
+    assert np.array_equal(vf.cpu().numpy()[..., 0], ref["valid"])
+    bound = dc.shade_fwd_bound(ref)
+    r_stmt = float((np.abs(pf.detach().cpu().numpy() - ref["pixels"]) / bound).max())
+    r_glue = float(((pf - pg).detach().abs().cpu().numpy() / bound).max())
+    gf, = torch.autograd.grad(dp.loss_fn(pf, vf, wts), [Vw], retain_graph=True)
+    gg, = torch.autograd.grad(dp.loss_fn(pg, vg, wts), [Vw])
+    rel_l2 = float(torch.linalg.norm(gf - gg) / torch.linalg.norm(gg))
+    print("chain 64x64: pixels %.3f of the bound against the statement, %.3f against the glue; "
+          "d loss / d world vertices rel L2 %.3g" % (r_stmt, r_glue, rel_l2))
+    assert r_stmt <= 1.0 and r_glue <= 1.0
+    assert bool(torch.isfinite(gf).all()) and float(gg.abs().max()) > 0
+    assert rel_l2 < 1e-2, rel_l2

@@ -6,6 +6,7 @@ each, the CPU oracle (test infrastructure, OpenMP on the job's host-core share) 
 
     python tools/bench_configs.py > profiles/r01/configs.jsonl
     python tools/bench_configs.py stress c5   # only the configs whose names contain these
+    python tools/bench_configs.py chain_rounds   # the c4 chain's six legs, three interleaved rounds
 """
 import json
 import os
@@ -86,25 +87,29 @@ def cpu_oracle(host, g, budget_s=3.0):
             "cpu_ms_per_step": round(t * 1e3, 2)}
 
 
-def deferred_chain(steps=20, batched=False, share=None):
+def deferred_chain(steps=20, batched=False, share=None, fused_shade=False):
     """c4 as the reference sample runs it: three 3-channel G-buffer renders + dilation + lighting + loss,
     backward to world-space vertices (tests/deferred_pipeline.py), through dirt_amd.rasterise + autograd.
     Reported eager (host-issued every step), as one captured HIP graph per step (device time: the whole
     chain replayed, no host work), and the host's issue time alone (eager wall time minus nothing queued).
     The unbatched chain renders one geometry three times: it opts into geometry sharing explicitly (`share`, default
     on for the unbatched chain; rasterise_ops.set_geometry_sharing, off by default in the library) and says so in its
-    label; share=False times the same chain with every render a full one."""
+    label; share=False times the same chain with every render a full one.
+    fused_shade: the pixel-space stage (dilation, validity, lighting) through dirt_amd.deferred.shade -- one launch
+    forward, one backward -- in place of the chain's framework-op glue (deferred_pipeline.shade); label
+    ..._fused_shade."""
     from dirt_amd import rasterise_ops
     share = (not batched) if share is None else bool(share)
     prev = rasterise_ops.set_geometry_sharing(share)
     try:
-        return _deferred_chain(steps, batched, share)
+        return _deferred_chain(steps, batched, share, fused_shade)
     finally:
         rasterise_ops.set_geometry_sharing(prev)
 
 
-def _deferred_chain(steps, batched, share):
+def _deferred_chain(steps, batched, share, fused_shade=False):
     import deferred_pipeline as dp
+    from dirt_amd import deferred
     dev = torch.device("cuda", 0)
     H = W = 512
     world, faces, albedo = dp.grid_surface()
@@ -114,8 +119,21 @@ def _deferred_chain(steps, batched, share):
     wts = torch.rand((H, W, 3), device=dev)
     out = {}
 
+    lights = None
+    if fused_shade:
+        # the sample's constants (samples/deferred.py:93-115): grey ambient, one directional light, red diffuse and
+        # white specular colours, the camera's world position
+        lights = (torch.tensor([0.2, 0.2, 0.2], device=dev), dp.unit([1., -0.3, -0.5]).to(dev),
+                  torch.tensor([1., 0., 0.], device=dev), torch.tensor([1., 1., 1.], device=dev),
+                  dp.camera_position(H, W, dev))
+
     def step():
-        L, _, _ = dp.chain(dp.hip_render, Vw, f, al, H, W, wts, batched=batched)
+        if fused_shade:
+            pos, col, nrm, _ = dp.gbuffers(dp.hip_render, Vw, f, al, H, W, batched=batched)
+            pixels, valid = deferred.shade(pos, col, nrm, *lights, 6., False)
+            L = dp.loss_fn(pixels, valid, wts)
+        else:
+            L, _, _ = dp.chain(dp.hip_render, Vw, f, al, H, W, wts, batched=batched)
         out["g"] = torch.autograd.grad(L, [Vw])[0]
 
     for _ in range(3):
@@ -135,7 +153,8 @@ def _deferred_chain(steps, batched, share):
     t_issue = (time.perf_counter() - t0) / steps
     torch.cuda.synchronize()
     res = {"config": "c4_deferred_chain_3x512x512x3_grad_to_world_vertices" + ("_batched" if batched else "") +
-           ("_shared_geometry" if share else ""), "geometry_sharing": share,
+           ("_shared_geometry" if share else "") + ("_fused_shade" if fused_shade else ""), "geometry_sharing": share,
+           "fused_shade": fused_shade,
            "faces": len(faces),
            "ms_per_step_eager": round(dt * 1e3, 3), "host_issue_ms_per_step": round(t_issue * 1e3, 3),
            "Mpixels_per_s_fwd_bwd": round(H * W / dt / 1e6, 1)}
@@ -164,6 +183,20 @@ def _deferred_chain(steps, batched, share):
     except Exception as e:  # noqa: BLE001 -- reported, not fatal
         res["graph_error"] = "%s: %s" % (type(e).__name__, str(e)[:200])
     return res
+
+
+CHAIN_LEGS = [dict(), dict(fused_shade=True), dict(share=False), dict(share=False, fused_shade=True),
+              dict(batched=True), dict(batched=True, fused_shade=True)]
+
+
+def chain_rounds(rounds=3):
+    """The six chain legs (glue and fused shade; unbatched with sharing, unbatched without, batched) interleaved,
+    `rounds` times in this process: one JSON line per leg and round (`python tools/bench_configs.py chain_rounds`)."""
+    for r in range(rounds):
+        for kw in CHAIN_LEGS:
+            res = deferred_chain(**kw)
+            res["round"] = r
+            print(json.dumps(res), flush=True)
 
 
 def run(name, frames, steps=100):
@@ -214,6 +247,8 @@ def run(name, frames, steps=100):
 def main():
     # optional arguments: substrings selecting configs (all by default)
     sel = sys.argv[1:]
+    if sel == ["chain_rounds"]:
+        return chain_rounds()
     for name, make in CONFIGS.items():
         if not sel or any(k in name for k in sel):
             print(json.dumps(run(name, make())), flush=True)
@@ -221,6 +256,9 @@ def main():
         print(json.dumps(deferred_chain()), flush=True)  # (opts into geometry sharing, labelled)
         print(json.dumps(deferred_chain(share=False)), flush=True)
         print(json.dumps(deferred_chain(batched=True)), flush=True)
+        print(json.dumps(deferred_chain(fused_shade=True)), flush=True)
+        print(json.dumps(deferred_chain(share=False, fused_shade=True)), flush=True)
+        print(json.dumps(deferred_chain(batched=True, fused_shade=True)), flush=True)
 
 
 if __name__ == "__main__":
