@@ -32,7 +32,9 @@ ABI_VERSION = 13
 FWD_SCRATCH_CLEAN = 1  # dirt_rasterise_fwd flags
 FWD_DEEP_CULL = 2      # dirt_rasterise_fwd: occluder culling for deep scenes (forced; automatic since ABI 12)
 FWD_DEEP_CULL_OFF = 8  # dirt_rasterise_fwd: never the occluder culling
-BWD_ACCUMULATE = 1     # dirt_rasterise_bwd / dirt_rasterise_bwd_recompute flags
+TEXTURE_CLAMP = 0      # dirt_texture_sample_* wrap modes
+TEXTURE_REPEAT = 1
+BWD_ACCUMULATE = 1    # dirt_rasterise_bwd / dirt_rasterise_bwd_recompute flags
 BWD_SCRATCH_CLEAN = 2  # dirt_rasterise_bwd_recompute: the workspace's bin counters are clean
 
 # every symbol include/dirt_mi355x.h declares, with its ctypes signature
@@ -73,6 +75,8 @@ SIGNATURES = {
     "dirt_deferred_shade_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
     "dirt_deferred_shade_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P,
                                      _P, _P]),
+    "dirt_texture_sample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "dirt_texture_sample_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dirt_last_error": (ctypes.c_char_p, []),
 }
 

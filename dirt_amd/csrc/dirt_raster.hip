@@ -269,6 +269,7 @@ struct EventPair {
 #include "grad_kernel.h"
 #include "lighting_kernels.h"
 #include "deferred_kernels.h"
+#include "texture_kernels.h"
 
 // zero two float arrays in one launch (the backward's atomically accumulated outputs)
 __global__ __launch_bounds__(256) void zero2_kernel(float *__restrict__ a, int64_t na, float *__restrict__ b, int64_t nb)
@@ -1520,6 +1521,107 @@ int dirt_deferred_shade_bwd(const float *positions, const float *colors, const f
                            double_sided};
     deferred_shade_bwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
         positions, colors, normals, H, W, n, L, grad_pixels, route, grad_positions, grad_colors, grad_normals);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- deferred texturing: bilinear texture sampling and its gradients (texture_kernels.h)
+
+namespace {
+
+// the argument checks of the two entry points beyond deferred_sizes'
+int texture_sizes(int texture_frames, int Th, int Tw, int B, int H, int W, int C, int wrap, int64_t *pixels)
+{
+    const int rc = deferred_sizes("texture_sample", B, H, W, C, pixels);
+    if (rc) return rc;
+    *pixels = 0;
+    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM)
+        return fail(DIRT_EINVAL, "texture_sample: texture height, width must be in 1..8192");
+    if (wrap != DIRT_TEXTURE_CLAMP && wrap != DIRT_TEXTURE_REPEAT)
+        return fail(DIRT_EINVAL, "texture_sample: wrap must be DIRT_TEXTURE_CLAMP or DIRT_TEXTURE_REPEAT");
+    if (B > 0 && texture_frames != 1 && texture_frames != B)
+        return fail(DIRT_EINVAL, "texture_sample: texture_frames must be 1 or the batch size");
+    const int64_t tiles = (int64_t)((H + kTexTile - 1) / kTexTile) * ((W + kTexTile - 1) / kTexTile);
+    if ((int64_t)B * tiles > 0x7fffffffLL)
+        return fail(DIRT_EINVAL, "texture_sample: too large (more screen tiles than one launch covers)");
+    *pixels = (int64_t)B * H * W;
+    return DIRT_OK;
+}
+
+// fn(std::integral_constant<int, C>{}) for the run-time channel count C in 1..DIRT_MAX_CHANNELS
+template <class Fn>
+void texture_channels(int C, Fn &&fn)
+{
+    switch (C) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    case 5: fn(std::integral_constant<int, 5>{}); break;
+    case 6: fn(std::integral_constant<int, 6>{}); break;
+    case 7: fn(std::integral_constant<int, 7>{}); break;
+    default: fn(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+template <int C>
+void launch_texture_fwd(const float *texture, int64_t frame_stride, int Th, int Tw, const float *uv,
+                        const uint8_t *mask, int64_t hw, int64_t n, int wrap, float *texels, uint8_t *valid,
+                        hipStream_t stream)
+{
+    texture_sample_fwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        texture, frame_stride, Th, Tw, uv, mask, hw, n, wrap, texels, valid);
+}
+
+template <int C>
+void launch_texture_bwd(const float *texture, int64_t frame_stride, int Th, int Tw, const float *uv,
+                        const uint8_t *mask, int B, int H, int W, int wrap, const float *grad, float *grad_texture,
+                        float *grad_uv, hipStream_t stream)
+{
+    const int tiles_x = (W + kTexTile - 1) / kTexTile, tiles_y = (H + kTexTile - 1) / kTexTile;
+    texture_sample_bwd_kernel<C><<<dim3((unsigned)((int64_t)B * tiles_y * tiles_x)), dim3(kLightThreads), 0, stream>>>(
+        texture, frame_stride, Th, Tw, uv, mask, H, W, tiles_x, tiles_y, wrap, grad, grad_texture, grad_uv);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_texture_sample_fwd(const float *texture, int texture_frames, int Th, int Tw, int C, const float *uv,
+                            const uint8_t *mask, int B, int H, int W, int wrap, float *texels, uint8_t *valid,
+                            void *stream_)
+{
+    int64_t n;
+    const int rc = texture_sizes(texture_frames, Th, Tw, B, H, W, C, wrap, &n);
+    if (rc || n == 0) return rc;
+    if (!texture || !uv || !texels || !valid) return fail(DIRT_EINVAL, "texture_sample: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = texture_frames == 1 ? 0 : (int64_t)Th * Tw * C, hw = (int64_t)H * W;
+    texture_channels(C, [&](auto c) {
+        launch_texture_fwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, hw, n, wrap, texels, valid, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_texture_sample_bwd(const float *texture, int texture_frames, int Th, int Tw, int C, const float *uv,
+                            const uint8_t *mask, int B, int H, int W, int wrap, const float *grad_texels,
+                            float *grad_texture, float *grad_uv, void *stream_)
+{
+    int64_t n;
+    const int rc = texture_sizes(texture_frames, Th, Tw, B, H, W, C, wrap, &n);
+    if (rc || n == 0 || (!grad_texture && !grad_uv)) return rc;
+    if (!texture || !uv || !grad_texels) return fail(DIRT_EINVAL, "texture_sample: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = texture_frames == 1 ? 0 : (int64_t)Th * Tw * C;
+    if (grad_texture)
+        HIP_TRY(hipMemsetAsync(grad_texture, 0, (size_t)texture_frames * Th * Tw * C * sizeof(float), stream));
+    texture_channels(C, [&](auto c) {
+        launch_texture_bwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, B, H, W, wrap, grad_texels, grad_texture,
+                                               grad_uv, stream);
+    });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }

@@ -77,7 +77,8 @@ extern "C" {
  * 11: + dirt_rasterise_fwd_stash, the recompute workspace grows by the gradient stash; 12: the Gouraud forward
  * picks the occluder culling by itself (DIRT_FWD_DEEP_CULL forces it, + DIRT_FWD_DEEP_CULL_OFF); 13: +
  * dirt_rasterise_fwd_resolve; added at 13 without a bump, no signature or layout changed: dirt_dilate_fwd,
- * dirt_dilate_bwd, dirt_deferred_shade_fwd, dirt_deferred_shade_bwd) */
+ * dirt_dilate_bwd, dirt_deferred_shade_fwd, dirt_deferred_shade_bwd, dirt_texture_sample_fwd,
+ * dirt_texture_sample_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -318,6 +319,37 @@ int dirt_deferred_shade_bwd(const float *positions, const float *colors, const f
                             const float *specular_color, const float *camera_position, float shininess,
                             int double_sided, const float *grad_pixels, const uint32_t *route, float *grad_positions,
                             float *grad_colors, float *grad_normals, void *stream);
+
+/* Deferred texturing: bilinear sampling of a texture at a uv G-buffer, and its gradients.
+ * texture [texture_frames,Th,Tw,C] (texture_frames = 1: shared by the B frames, = B: one per frame), uv [B,H,W,2],
+ * mask [B,H,W] uint8 (NULL = "both uv channels are finite"), texels [B,H,W,C], valid [B,H,W] uint8 (0 / 1).
+ * u runs along the texture's width, v along its height, the top row first; texel (i,j) has its centre at
+ * u = (j + 0.5) / Tw, v = (i + 0.5) / Th.  H, W, Th, Tw in 1..DIRT_MAX_DIM, C in 1..DIRT_MAX_CHANNELS, B >= 0
+ * (B == 0: no-op).  Rule, float32, every step one IEEE operation; for u with T = Tw (v with Th alike):
+ *   DIRT_TEXTURE_CLAMP (GL CLAMP_TO_EDGE): uc = min(max(u, 0), 1)      DIRT_TEXTURE_REPEAT: uc = u - floor(u)
+ *   x = uc * T;  x = x - 0.5;  fx = floor(x);  a = x - fx;  j0 = (int)fx;  j1 = j0 + 1
+ *   j0, j1 reduced into [0, T): clamped, or modulo T in repeat mode (uc may round to exactly 1: j1 = T -> 0)
+ * (fx is clamped to [-1, T] and a NaN sent to -1 before the conversion: no uv, finite or not, addresses outside the
+ * texture.)  Per channel, each product and sum rounded once in this order:
+ *   top = t[i0,j0] * (1 - a) + t[i0,j1] * a;  bot = t[i1,j0] * (1 - a) + t[i1,j1] * a;  out = top * (1 - b) + bot * b
+ * Pixels that are not sampled give exactly 0 and valid 0, carry no gradient and form no address.
+ * Backward, with g = grad_texels[p,:] at sampled pixels:
+ *   grad_texture[i0,j0,c] += g_c * (1 - a) * (1 - b), and likewise for the other three taps;
+ *   grad_u = pass_u ? Tw * sum_c g_c * ((t[i0,j1] - t[i0,j0]) * (1 - b) + (t[i1,j1] - t[i1,j0]) * b) : 0
+ *   grad_v = pass_v ? Th * sum_c g_c * (bot_c - top_c) : 0;   pass_u: 0 <= u <= 1 (clamp), always (repeat).
+ * grad_texture [texture_frames,Th,Tw,C] is zero-filled on `stream` by the call (an asynchronous memset, capturable)
+ * and fully overwritten; with texture_frames = 1 it sums over the frames.  It is summed with float atomics: the
+ * result may differ in the last bits between calls (as dirt_vertex_normals_*).  grad_uv [B,H,W,2] is fully
+ * overwritten, zero at unsampled pixels; it is a gather in a fixed order, bit-identical from run to run.  Either
+ * gradient may be NULL; with both NULL the backward returns DIRT_OK without a launch. */
+#define DIRT_TEXTURE_CLAMP 0
+#define DIRT_TEXTURE_REPEAT 1
+int dirt_texture_sample_fwd(const float *texture, int texture_frames, int Th, int Tw, int C, const float *uv,
+                            const uint8_t *mask, int B, int H, int W, int wrap, float *texels, uint8_t *valid,
+                            void *stream);
+int dirt_texture_sample_bwd(const float *texture, int texture_frames, int Th, int Tw, int C, const float *uv,
+                            const uint8_t *mask, int B, int H, int W, int wrap, const float *grad_texels,
+                            float *grad_texture, float *grad_uv, void *stream);
 
 /* Thread-local message for the last non-OK return on this thread. */
 const char *dirt_last_error(void);

@@ -1,0 +1,365 @@
+"""The fused texture-sampling kernels (dirt_amd/csrc/texture_kernels.h through dirt_amd.deferred.sample_texture) against
+the numpy statement of record (tests/texture_cases.py) on its whole table.
+
+Forward and valid: bit-exact against the float32 statement, unsampled pixels exactly 0.
+grad_uv: bit-identical between two runs (a gather in a fixed order), and within k * 2^-24 * (sum of the absolute
+terms) of the float64 statement, k = C + 5: one channel's term passes through at most five float32 roundings (the texel
+difference -- or the product and sum inside top / bot --, the product with the weight, the sum of the two products, the
+product with g, the product with Tw or Th), the C terms are summed by C - 1 additions, one unit for the second order.
+grad_texture: within (n + k) * 2^-24 * S per element, n the number of nonzero terms, S the sum of their absolute
+values, k = 2: a term g * w1 * w2 is two float32 products of the float32 weights the statement hands over; the n terms
+are summed by n - 1 additions in whatever order the atomics arrive and however they are grouped (LDS patch first or
+not), each rounding a partial sum of at most S; the n-th unit absorbs the second-order terms.
+Each test prints its worst measured ratio of error to bound.
+"""
+import gc
+
+import numpy as np
+import pytest
+import torch
+
+import deferred_cases as dc
+import deferred_pipeline as dp
+import texture_cases as tc
+from dirt_amd import _lib, deferred
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+
+
+def _gpu(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _fused_node(y, cls):
+    """y comes from the fused autograd function `cls` (directly, or through the [0] of an unbatched call)"""
+    assert y.grad_fn is not None
+    names = [y.grad_fn.name()] + [fn.name() for fn, _ in y.grad_fn.next_functions if fn is not None]
+    assert any(cls in n for n in names), names
+
+
+def _run(inputs, needs=(True, True)):
+    """-> (texels, valid, grad_texture or None, grad_uv or None) as numpy"""
+    texture, uv, mask, wrap, grad = inputs
+    tt, ut = _gpu(texture).requires_grad_(needs[0]), _gpu(uv).requires_grad_(needs[1])
+    texels, valid = deferred.sample_texture(tt, ut, _gpu(mask), wrap)
+    assert not valid.requires_grad
+    if any(needs):
+        _fused_node(texels, "_SampleTextureFn")
+        texels.backward(_gpu(grad))
+    torch.cuda.synchronize()
+    return (texels.detach().cpu().numpy(), valid.cpu().numpy(), None if tt.grad is None else tt.grad.cpu().numpy(),
+            None if ut.grad is None else ut.grad.cpu().numpy())
+
+
+def _ratio(err, bound, tag):
+    """worst err / bound; where the bound is 0 the error must be"""
+    err, bound = np.asarray(err, np.float64), np.asarray(bound, np.float64)
+    zero = bound == 0
+    assert not np.any(err[zero]), tag
+    return float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
+
+
+def _check_forward(got, fwd, tag):
+    texels, valid = got[0], got[1]
+    assert valid.dtype == np.bool_ and valid.shape == fwd["valid"].shape + (1,), tag
+    assert np.array_equal(valid[..., 0], fwd["valid"]), tag
+    assert np.array_equal(_bits(texels), _bits(fwd["texels"])), tag
+    assert not np.any(_bits(texels)[~fwd["valid"]]), tag
+
+
+def _check_grads(got, vjp, C, tag):
+    """-> worst ratios (grad_texture, grad_uv) of error to bound, of the gradients present"""
+    rt = ru = 0.0
+    if got[2] is not None:
+        assert got[2].shape == vjp["grad_texture"].shape, tag
+        rt = _ratio(np.abs(got[2] - vjp["grad_texture"]), tc.texture_bound(vjp), tag)
+        assert rt <= 1.0, (tag, "grad_texture", rt)
+    if got[3] is not None:
+        ru = _ratio(np.abs(got[3] - vjp["grad_uv"]), tc.uv_bound(vjp, C), tag)
+        assert ru <= 1.0, (tag, "grad_uv", ru)
+    return rt, ru
+
+
+@pytest.mark.parametrize("ident", tc.CASE_IDS)
+def test_matches_the_statement(ident):
+    inputs, fwd, vjp = tc.case(ident)
+    C = inputs[0].shape[-1]
+    first, second = _run(inputs), _run(inputs)
+    _check_forward(first, fwd, ident)
+    assert np.array_equal(_bits(first[3]), _bits(second[3])), ident  # grad_uv: no run-to-run difference
+    assert not np.any(_bits(first[3])[~fwd["valid"]]), ident
+    rt, ru = _check_grads(first, vjp, C, ident)
+    rt2, _ = _check_grads(second, vjp, C, ident)
+    print("texture %s: grad_texture %.3f of its bound, grad_uv %.3f of its bound" % (ident, max(rt, rt2), ru))
+
+
+@pytest.mark.parametrize("kind,C,frames", [("magnify16", 3, 1), ("scatter", 3, 1), ("magnify16", 8, 2),
+                                           ("scatter", 4, 2)])
+def test_exact_scatter(kind, C, frames):
+    """Weights in {0, 1/4, 1/2, 1} and small integer cotangents: every partial sum is exact in float32, so
+    grad_texture equals the statement exactly whatever the order of the atomics -- through the LDS patch and its
+    flush (magnify16), through the direct atomics (scatter), and summed over the frames of a shared texture."""
+    inputs, fwd, vjp = tc.exact_scatter_case(kind, C, frames)
+    got = _run(inputs)
+    _check_forward(got, fwd, kind)
+    assert np.array_equal(got[2].astype(np.float64), vjp["grad_texture"]), kind
+    assert np.array_equal(got[3].astype(np.float64), vjp["grad_uv"]), kind  # (exact too: small integers and halves)
+    assert np.count_nonzero(vjp["grad_texture"]) > 0
+
+
+@pytest.mark.parametrize("needs", [(False, False), (True, False), (False, True)], ids=["none", "texture", "uv"])
+def test_gradient_subsets(needs):
+    """Only the texture, only the uv, neither: the requested gradient as the both-run's (grad_uv bit for bit,
+    grad_texture within the bound), the others None."""
+    ident = "63x65-t5x7-c3-perframe-random-clamp-bg"
+    inputs, fwd, vjp = tc.case(ident)
+    got, full = _run(inputs, needs), _run(inputs)
+    _check_forward(got, fwd, ident)
+    assert (got[2] is not None) == needs[0] and (got[3] is not None) == needs[1]
+    _check_grads(got, vjp, 3, "subset %s" % (needs,))
+    if needs[1]:
+        assert np.array_equal(_bits(got[3]), _bits(full[3]))
+    if needs[0]:
+        assert np.all(np.abs(got[2] - full[2]) <= 2 * tc.texture_bound(vjp))
+
+
+def test_forms(monkeypatch):
+    """[H,W,2] with a shared texture, non-contiguous views, bool and integer masks run the fused kernels; float64
+    and DIRT_FUSED_DEFERRED=0 take the statement, with no fused node."""
+    ident = "15x17-t5x7-c3-shared-exact-clamp"
+    (texture, uv, _, wrap, grad), fwd, vjp = tc.case(ident)
+    mask = (np.random.default_rng(2).random(uv.shape[:-1]) < 0.7).astype(np.uint8)
+    fwd = tc.sample(texture, uv, mask, wrap)
+    vjp = tc.sample_vjp(texture, grad, fwd)
+    base = _run((texture, uv, mask, wrap, grad))
+    _check_forward(base, fwd, ident)
+    _check_grads(base, vjp, 3, ident)
+    # unbatched, bool mask
+    tt, ut = _gpu(texture).requires_grad_(True), _gpu(uv[0]).requires_grad_(True)
+    texels, valid = deferred.sample_texture(tt, ut, _gpu(mask[0]).bool(), wrap)
+    _fused_node(texels, "_SampleTextureFn")
+    assert texels.shape == (15, 17, 3) and valid.shape == (15, 17, 1) and valid.dtype == torch.bool
+    texels.backward(_gpu(grad[0]))
+    assert np.array_equal(_bits(texels.detach().cpu().numpy()), _bits(base[0][0]))
+    assert np.array_equal(_bits(ut.grad.cpu().numpy()), _bits(base[3][0]))
+    assert np.all(np.abs(tt.grad.cpu().numpy() - vjp["grad_texture"]) <= tc.texture_bound(vjp))
+    # non-contiguous views, integer mask
+    wide_t, wide_u = torch.zeros((5, 7, 6), device=DEV), torch.zeros((1, 15, 17, 4), device=DEV)
+    wide_t[..., ::2], wide_u[..., ::2] = _gpu(texture), _gpu(uv)
+    wide_t.requires_grad_(True), wide_u.requires_grad_(True)
+    assert not wide_t[..., ::2].is_contiguous()
+    texels, valid = deferred.sample_texture(wide_t[..., ::2], wide_u[..., ::2], _gpu(mask).long(), wrap)
+    _fused_node(texels, "_SampleTextureFn")
+    texels.backward(_gpu(grad))
+    assert np.array_equal(_bits(texels.detach().cpu().numpy()), _bits(base[0]))
+    assert np.array_equal(_bits(wide_u.grad.cpu().numpy()[..., ::2]), _bits(base[3]))
+    assert float(wide_u.grad[..., 1::2].abs().max()) == 0.0 and float(wide_t.grad[..., 1::2].abs().max()) == 0.0
+    assert np.all(np.abs(wide_t.grad.cpu().numpy()[..., ::2] - vjp["grad_texture"]) <= tc.texture_bound(vjp))
+    # float64 and the switch: the framework-op statement
+    f64 = tc.sample(texture, uv, mask, wrap, np.float64)
+    t64 = _gpu(texture).double().requires_grad_(True)
+    y64, v64 = deferred.sample_texture(t64, _gpu(uv).double(), _gpu(mask), wrap)
+    assert "_SampleTextureFn" not in y64.grad_fn.name()
+    assert np.abs(y64.detach().cpu().numpy() - f64["texels"]).max() <= 1e-12
+    monkeypatch.setattr(deferred, "_FUSED_ENABLED", False)
+    tt = _gpu(texture).requires_grad_(True)
+    y, v = deferred.sample_texture(tt, _gpu(uv), _gpu(mask), wrap)
+    assert "_SampleTextureFn" not in y.grad_fn.name()
+    assert np.array_equal(v.cpu().numpy()[..., 0], fwd["valid"])
+    # (four roundings on any path from a texel to the output, whatever the framework's kernels contract)
+    assert np.abs(y.detach().cpu().numpy() - fwd["texels"]).max() <= 5 * 2.0 ** -24 * np.abs(texture).max()
+
+
+def test_fused_backward_refuses_double_backward(monkeypatch):
+    (texture, uv, mask, wrap, grad), _, _ = tc.case("15x17-t5x7-c3-shared-exact-clamp")
+    tt, ut = _gpu(texture).requires_grad_(True), _gpu(uv).requires_grad_(True)
+    texels, _ = deferred.sample_texture(tt, ut, None, wrap)
+    with pytest.raises(RuntimeError, match="create_graph"):
+        torch.autograd.grad(texels.square().sum(), [tt], create_graph=True)
+    monkeypatch.setattr(deferred, "_FUSED_ENABLED", False)
+    texels, _ = deferred.sample_texture(tt, ut, None, wrap)
+    g, = torch.autograd.grad(texels.square().sum(), [ut], create_graph=True)
+    gg, = torch.autograd.grad(g.square().sum(), [tt])
+    assert bool(torch.isfinite(gg).all())
+
+
+def test_offsets_past_2_31():
+    """A per-frame texture [5, 8192, 8192, 8]: 2.68e9 elements, the smallest allowed shape whose element offsets (of
+    the last frame) do not fit a signed 32-bit index.  A 4 x 4 uv frame per texture probes the four corners and the
+    end of the last frame at half-texel positions (weights in {0, 1/4, 1/2, 1}); forward and grad_texture on the
+    probes against the statement, exactly, and nothing else nonzero, frame by frame.  Two 10.7 GB tensors are alive
+    at a time and the allocator's blocks are released at the end."""
+    B, T, C = 5, 8192, 8
+    assert B * T * T * C > 2 ** 31 >= (B - 1) * T * T * C  # (four frames end exactly at the last int32 offset)
+    rng = np.random.default_rng(13)
+    # x = k / 2 - 0.5: k = 0 (u = 0) and 2T (u = 1) put both taps on one edge texel, the others on texels 0..1, T-2..T-1
+    ks = np.array([0, 1, 2, 2 * T - 3, 2 * T - 2, 2 * T - 1, 2 * T])
+    pick = rng.integers(0, 7, (B, 4, 4, 2))
+    pick[0] = rng.integers(0, 3, (4, 4, 2))      # the first frame: its first corner alone (the box fits the patch)
+    pick[B - 1] = rng.integers(3, 7, (4, 4, 2))  # the last frame: its last corner alone, patch and flush past 2^31
+    uv = (ks[pick] / (2.0 * T)).astype(np.float32)
+    uv[B - 1, 3, 3] = (2 * T - 1) / (2.0 * T)  # the last texel of the last frame
+    uv[0, 0, 0] = 1 / (2.0 * T)                # the first of the first
+    uv[2, 1, 1] = -np.inf
+    grad = rng.integers(1, 4, (B, 4, 4, C)).astype(np.float32)
+    lib, stream = _lib.load(), torch.cuda.current_stream(DEV).cuda_stream
+    corner = [slice(0, 2), slice(T - 2, T)]
+    try:
+        texture = torch.zeros((B, T, T, C), device=DEV)
+        for ys in corner:
+            for xs in corner:
+                texture[:, ys, xs] = _gpu(rng.integers(1, 5, (B, 2, 2, C)).astype(np.float32))
+
+        def fetch(f, i, j):
+            f, i, j = (torch.from_numpy(np.broadcast_to(a, i.shape).copy()).to(DEV) for a in (f, i, j))
+            return texture[f, i, j].cpu().numpy()
+
+        fwd = tc.sample((B, T, T, C), uv, None, "clamp", fetch=fetch)
+        ut, gt_ = _gpu(uv), _gpu(grad)
+        texels = torch.empty((B, 4, 4, C), device=DEV)
+        valid = torch.empty((B, 4, 4), dtype=torch.uint8, device=DEV)
+        _lib.check(lib.dirt_texture_sample_fwd(texture.data_ptr(), B, T, T, C, ut.data_ptr(), None, B, 4, 4,
+                                               _lib.TEXTURE_CLAMP, texels.data_ptr(), valid.data_ptr(), stream))
+        assert np.array_equal(valid.cpu().numpy() != 0, fwd["valid"]) and not fwd["valid"][2, 1, 1]
+        assert np.array_equal(_bits(texels.cpu().numpy()), _bits(fwd["texels"]))
+        assert int(np.count_nonzero(fwd["texels"])) == C * (B * 16 - 1)
+        grad_texture = torch.empty_like(texture)  # (uninitialised: the call zero-fills it)
+        grad_uv = torch.empty((B, 4, 4, 2), device=DEV)
+        _lib.check(lib.dirt_texture_sample_bwd(texture.data_ptr(), B, T, T, C, ut.data_ptr(), None, B, 4, 4,
+                                               _lib.TEXTURE_CLAMP, gt_.data_ptr(), grad_texture.data_ptr(),
+                                               grad_uv.data_ptr(), stream))
+        torch.cuda.synchronize()
+        # the statement's scatter on the corner blocks alone (every tap lies in one)
+        want = np.zeros((B, 4, 4, C))
+        fold = lambda i: np.where(i < 2, i, i - (T - 4))  # noqa: E731  (0, 1, T-2, T-1 -> 0, 1, 2, 3)
+        v = fwd["valid"]
+        for ii, jj, w in ((fwd["i0"], fwd["j0"], fwd["oma"] * fwd["omb"]), (fwd["i0"], fwd["j1"], fwd["a"] * fwd["omb"]),
+                          (fwd["i1"], fwd["j0"], fwd["oma"] * fwd["b"]), (fwd["i1"], fwd["j1"], fwd["a"] * fwd["b"])):
+            assert np.all((ii[v] < 2) | (ii[v] >= T - 2)) and np.all((jj[v] < 2) | (jj[v] >= T - 2))
+            np.add.at(want, (fwd["frame"][v], fold(ii[v]), fold(jj[v])),
+                      grad[v].astype(np.float64) * w[v][:, None].astype(np.float64))
+        for b in range(B):
+            got = torch.cat([torch.cat([grad_texture[b, ys, xs] for xs in corner], 1) for ys in corner], 0)
+            assert np.array_equal(got.cpu().numpy().astype(np.float64), want[b]), b
+            assert int(torch.count_nonzero(grad_texture[b])) == int(np.count_nonzero(want[b])), b
+        assert np.count_nonzero(want[B - 1, 3, 3]) == C and np.count_nonzero(want[0, 0, 0]) == C
+        assert bool(torch.isfinite(grad_uv).all())
+    finally:
+        texture = grad_texture = None
+        gc.collect()
+        torch.cuda.empty_cache()
+
+
+def test_captures_into_a_graph():
+    """One forward and backward captured with torch.cuda.graph on one stream (no parallel branches; the zero-fill of
+    grad_texture is an asynchronous memset on it), replayed after uv and texture changed in place: equal to the eager
+    result, grad_uv bit for bit, grad_texture within the bound."""
+    first = tc.case("63x65-t64x64-c3-shared-magnify16-clamp-bg")[0]
+    second = tc.case("63x65-t5x7-c3-perframe-random-clamp-bg")[0]
+    # the same shapes are needed: the second case's uv and cotangent over a re-seeded 64 x 64 texture
+    texture2 = np.random.default_rng(21).standard_normal(first[0].shape).astype(np.float32)
+    second = (texture2, second[1], None, "clamp", second[4])
+    fwd2 = tc.sample(*second[:4])
+    vjp2 = tc.sample_vjp(texture2, second[4], fwd2)
+    assert 0.2 < fwd2["valid"].mean() < 0.9 and np.count_nonzero(vjp2["grad_texture"]) > 1000
+    tt, ut = _gpu(first[0]).requires_grad_(True), _gpu(first[1]).requires_grad_(True)
+    g = _gpu(second[4])
+    out = {}
+
+    def step():
+        texels, valid = deferred.sample_texture(tt, ut, None, "clamp")
+        out["texels"], out["valid"] = texels, valid
+        out["grads"] = torch.autograd.grad(texels, [tt, ut], g)
+
+    gc.collect()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    out.clear()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    with torch.no_grad():
+        tt.copy_(_gpu(second[0]))
+        ut.copy_(_gpu(second[1]))
+    graph.replay()
+    torch.cuda.synchronize()
+    got = (out["texels"].detach().cpu().numpy(), out["valid"].cpu().numpy(), out["grads"][0].cpu().numpy(),
+           out["grads"][1].cpu().numpy())
+    del graph
+    out.clear()
+    eager = _run(second)
+    _check_forward(got, fwd2, "graph")
+    assert np.array_equal(_bits(got[0]), _bits(eager[0])) and np.array_equal(got[1], eager[1])
+    assert np.array_equal(_bits(got[3]), _bits(eager[3]))
+    rt, ru = _check_grads(got, vjp2, 3, "graph")
+    print("graph replay: grad_texture %.3f of its bound, grad_uv %.3f of its bound" % (rt, ru))
+
+
+def test_chain_textured_deferred_shading():
+    """The deferred chain at 64 x 64 over dp.grid_surface(n=12) with a texture: per-vertex uv from the surface's own
+    x and y (u = x / 2.8 + 0.5, v = 2 y + 0.5), rendered as a 2-channel G-buffer over -inf, dilated, looked up in a
+    16 x 16 x 3 texture, and the texels shaded by deferred.shade as the colours.  The fused lookup against
+    `_sample_texture_ops` on the GPU, everything else shared: valid equal; pixels within the shade's forward contract;
+    d loss / d texture within the scatter bound of the statement; d loss / d world vertices within 1e-2 in relative
+    L2 (the tolerance of test_chain_with_the_fused_shade_against_the_pipeline_glue for it).  d loss / d texture
+    against the framework ops' is held to 1e-4 of its scale besides (tests/lighting_cases.py's GRAD_FRAC).
+    Measured on an MI355X: pixels 0.007 of the bound, d loss / d texture 0.435 of the scatter bound and 1.3e-7 to
+    2.7e-7 of its scale from the framework ops', d loss / d world vertices 1.0e-7 to 1.3e-7 in relative L2."""
+    H = W = 64
+    world, faces, albedo = dp.grid_surface(n=12)
+    f, al = _gpu(faces), _gpu(albedo)
+    wts = torch.rand((H, W, 3), device=DEV, generator=torch.Generator(device=DEV).manual_seed(3))
+    tex0 = torch.rand((16, 16, 3), device=DEV, generator=torch.Generator(device=DEV).manual_seed(4)) * 0.8 + 0.2
+    grey, ld, red, white = dp._constants(DEV)
+    cam = dp.camera_position(H, W, DEV)
+    ninf2 = torch.full((H, W, 2), float("-inf"), device=DEV)
+
+    def chain(lookup):
+        Vw, tex = _gpu(world).requires_grad_(True), tex0.clone().requires_grad_(True)
+        pos, _, nrm, clip = dp.gbuffers(dp.hip_render, Vw, f, al, H, W)
+        vertex_uv = torch.stack([Vw[:, 0] / 2.8 + 0.5, Vw[:, 1] * 2.0 + 0.5], -1)
+        uvbuf = deferred.dilate(dp.hip_render(ninf2, clip, vertex_uv, f, H, W, 2))
+        colours, sampled = lookup(tex, uvbuf)
+        pixels, valid = deferred.shade(pos, colours, nrm, grey, ld, red, white, cam, 6., False)
+        g_tex, g_v = torch.autograd.grad(dp.loss_fn(pixels, valid, wts), [tex, Vw], retain_graph=True)
+        g_col, = torch.autograd.grad(dp.loss_fn(pixels, valid, wts), [colours])
+        return dict(pixels=pixels.detach(), valid=valid, sampled=sampled, colours=colours, uvbuf=uvbuf.detach(),
+                    g_tex=g_tex, g_v=g_v, g_col=g_col, pos=pos.detach(), nrm=nrm.detach())
+
+    fused = chain(lambda t, u: deferred.sample_texture(t, u))
+    _fused_node(fused["colours"], "_SampleTextureFn")
+    ops = chain(lambda t, u: deferred._sample_texture_ops(t, u))
+    assert torch.equal(fused["valid"], ops["valid"]) and torch.equal(fused["sampled"], ops["sampled"])
+    assert bool(fused["valid"].any()) and not bool(fused["valid"].all()) and bool(fused["sampled"].any())
+    assert bool((fused["valid"] & fused["sampled"]).any())
+    # pixels: the shade's forward contract, around the statement's shading of the ops path's colours
+    L = dc.Lights(camera=cam.cpu().numpy())
+    L.ambient, L.direction, L.diffuse, L.specular = (t.cpu().numpy() for t in (grey, ld, red, white))
+    ref = dc.shade(ops["pos"].cpu().numpy(), ops["colours"].detach().cpu().numpy(), ops["nrm"].cpu().numpy(), L)
+    r_px = _ratio((fused["pixels"] - ops["pixels"]).abs().cpu().numpy(), dc.shade_fwd_bound(ref), "chain pixels")
+    # d loss / d texture: the statement's scatter of the fused path's own colour cotangent
+    uv_np = fused["uvbuf"].cpu().numpy()[None]
+    fwd = tc.sample(tex0.cpu().numpy(), uv_np)
+    assert np.array_equal(fwd["valid"][0], fused["sampled"].cpu().numpy()[..., 0])
+    assert np.array_equal(_bits(fused["colours"].detach().cpu().numpy()), _bits(fwd["texels"][0]))
+    vjp = tc.sample_vjp(tex0.cpu().numpy(), fused["g_col"].cpu().numpy()[None], fwd)
+    r_tex = _ratio(np.abs(fused["g_tex"].cpu().numpy() - vjp["grad_texture"]), tc.texture_bound(vjp), "chain texture")
+    scale = float(ops["g_tex"].abs().max())
+    d_tex = float((fused["g_tex"] - ops["g_tex"]).abs().max()) / scale
+    rel_l2 = float(torch.linalg.norm(fused["g_v"] - ops["g_v"]) / torch.linalg.norm(ops["g_v"]))
+    print("textured chain 64x64: pixels %.3f of the bound, d loss / d texture %.3f of the scatter bound (%.3g of its "
+          "scale from the framework ops'), d loss / d world vertices rel L2 %.3g" % (r_px, r_tex, d_tex, rel_l2))
+    assert r_px <= 1.0 and r_tex <= 1.0
+    assert scale > 0 and d_tex <= 1e-4
+    assert bool(torch.isfinite(fused["g_v"]).all()) and float(ops["g_v"].abs().max()) > 0
+    assert rel_l2 < 1e-2, rel_l2

@@ -1,0 +1,313 @@
+"""Statement of record for deferred texturing (dirt_amd.deferred.sample_texture, dirt_amd/csrc/texture_kernels.h), and
+its table of cases.  numpy only, no torch and no code shared with either implementation.  TEST INFRASTRUCTURE ONLY.
+
+Rule, in the arithmetic `dtype` (float32: the kernels' statement, every line one IEEE operation); for u with T = Tw
+(v with Th alike):
+  clamp:  uc = min(max(u, 0), 1)          repeat:  uc = u - floor(u)   (may round to exactly 1)
+  x = uc * T;  x = x - 0.5;  fx = floor(x);  a = x - fx;  j0 = (int)fx;  j1 = j0 + 1
+  j0, j1 reduced into [0, T) by clamping (clamp) or modulo T (repeat)
+  top = t[i0,j0] * (1 - a) + t[i0,j1] * a;  bot = t[i1,j0] * (1 - a) + t[i1,j1] * a;  out = top * (1 - b) + bot * b
+Texel (i, j) has its centre at u = (j + 0.5) / Tw, v = (i + 0.5) / Th; u runs along the width, the top row first.
+A pixel is sampled where mask != 0 (mask None: both uv channels finite); the others give exactly 0, no gradient.
+
+sample_vjp takes the forward's coordinates and weights (a, b, 1 - a, 1 - b as the forward rounded them) and does every
+product and sum in float64:
+  grad_texture[i0,j0,c] += g_c * (1 - a) * (1 - b)   and likewise for the other three taps
+  grad_u = pass_u ? Tw * sum_c g_c * ((t[i0,j1] - t[i0,j0]) * (1 - b) + (t[i1,j1] - t[i1,j0]) * b) : 0
+  grad_v = pass_v ? Th * sum_c g_c * (bot_c - top_c) : 0       pass: 0 <= u <= 1 (clamp), always (repeat)
+with, per texture element, the number n of nonzero terms and the sum S of their absolute values, and for grad_uv the
+sums of the absolute terms (every product taken with absolute factors, differences of texels as |difference| for
+grad_u and as the four |texel| * weight products for grad_v).
+"""
+import functools
+
+import numpy as np
+
+import deferred_cases
+
+F32 = np.float32
+WRAPS = ("clamp", "repeat")
+
+
+def _axis(u, T, wrap, dt):
+    """-> (i0, i1 int64 reduced into [0, T), a, pass) for the coordinate array u"""
+    u = np.asarray(u, dt)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if wrap == "repeat":
+            uc = u - np.floor(u)
+            ok = np.ones(u.shape, bool)
+        else:
+            uc = np.minimum(np.maximum(u, dt(0)), dt(1))
+            ok = (u >= 0) & (u <= 1)
+        x = uc * dt(T)
+        x = x - dt(0.5)
+        fx = np.floor(x)
+        a = x - fx
+        j0 = np.where(fx >= 0, np.minimum(fx, dt(T)), dt(-1))  # (a NaN compares false: -1)
+    assert uc.dtype == dt and a.dtype == dt
+    j0 = j0.astype(np.int64)
+    j1 = j0 + 1
+    if wrap == "repeat":
+        return np.mod(j0, T), np.mod(j1, T), a, ok
+    return np.clip(j0, 0, T - 1), np.clip(j1, 0, T - 1), a, ok
+
+
+def sample(texture, uv, mask=None, wrap="clamp", dtype=F32, fetch=None):
+    """texture [Th,Tw,C] or [Tf,Th,Tw,C] (Tf == B), uv [B,H,W,2], mask [B,H,W] or None -> dict: texels [B,H,W,C]
+    (dtype), valid [B,H,W] bool, the taps i0, i1, j0, j1, the weights a, b, oma, omb and pass_u, pass_v, all [B,H,W].
+    With `fetch`, texture is only its 4-D shape and fetch(f, i, j) -> [B,H,W,C] reads the texels (a texture too large
+    for the host)."""
+    assert wrap in WRAPS
+    dt = np.dtype(dtype).type
+    uv = np.asarray(uv, dt)
+    B, H, W, _ = uv.shape
+    if fetch is None:
+        t = np.asarray(texture, dt)
+        t = t[None] if t.ndim == 3 else t
+        Tf, Th, Tw, C = t.shape
+        fetch = lambda f, i, j: t[f, i, j]  # noqa: E731
+    else:
+        Tf, Th, Tw, C = texture
+    assert Tf in (1, B)
+    valid = np.isfinite(uv).all(-1) if mask is None else (np.asarray(mask).reshape(B, H, W) != 0)
+    uvs = np.where(valid[..., None], uv, dt(0))  # no index is formed from an unsampled pixel's uv
+    j0, j1, a, pu = _axis(uvs[..., 0], Tw, wrap, dt)
+    i0, i1, b, pv = _axis(uvs[..., 1], Th, wrap, dt)
+    f = np.zeros((B, 1, 1), np.int64) if Tf == 1 else np.arange(B)[:, None, None]
+    oma, omb = dt(1) - a, dt(1) - b
+    A, Bw, OA, OB = a[..., None], b[..., None], oma[..., None], omb[..., None]
+    top = np.asarray(fetch(f, i0, j0), dt) * OA + np.asarray(fetch(f, i0, j1), dt) * A
+    bot = np.asarray(fetch(f, i1, j0), dt) * OA + np.asarray(fetch(f, i1, j1), dt) * A
+    out = top * OB + bot * Bw
+    assert out.dtype == dt
+    return {"texels": np.where(valid[..., None], out, dt(0)), "valid": valid, "frame": np.broadcast_to(f, valid.shape),
+            "i0": i0, "i1": i1, "j0": j0, "j1": j1, "a": a, "b": b, "oma": oma, "omb": omb,
+            "pass_u": pu & valid, "pass_v": pv & valid}
+
+
+def sample_vjp(texture, grad, fwd):
+    """-> dict: grad_texture (float64, texture's shape), n, S (same shape), grad_uv [B,H,W,2], abs_uv [B,H,W,2]"""
+    t = np.asarray(texture, np.float64)
+    shared = t.ndim == 3
+    t = t[None] if shared else t
+    Tf, Th, Tw, C = t.shape
+    v = fwd["valid"]
+    g = np.where(v[..., None], np.asarray(grad, np.float64), 0.0)
+    a, b, oma, omb = (np.asarray(fwd[k], np.float64)[..., None] for k in ("a", "b", "oma", "omb"))
+    f, i0, i1, j0, j1 = (fwd[k] for k in ("frame", "i0", "i1", "j0", "j1"))
+    gt, n, S = np.zeros(t.shape), np.zeros(t.shape, np.int64), np.zeros(t.shape)
+    for ii, jj, w in ((i0, j0, oma * omb), (i0, j1, a * omb), (i1, j0, oma * b), (i1, j1, a * b)):
+        term = (g * w)[v]
+        idx = (f[v], ii[v], jj[v])
+        np.add.at(gt, idx, term)
+        np.add.at(S, idx, np.abs(term))
+        np.add.at(n, idx, (term != 0).astype(np.int64))
+    t00, t01, t10, t11 = t[f, i0, j0], t[f, i0, j1], t[f, i1, j0], t[f, i1, j1]
+    du = (t01 - t00) * omb + (t11 - t10) * b
+    top, bot = t00 * oma + t01 * a, t10 * oma + t11 * a
+    gu = np.where(fwd["pass_u"], Tw * (g * du).sum(-1), 0.0)
+    gv = np.where(fwd["pass_v"], Th * (g * (bot - top)).sum(-1), 0.0)
+    au = Tw * (np.abs(g) * (np.abs(t01 - t00) * omb + np.abs(t11 - t10) * b)).sum(-1)
+    av = Th * (np.abs(g) * ((np.abs(t00) + np.abs(t10)) * oma + (np.abs(t01) + np.abs(t11)) * a)).sum(-1)
+    out = {"grad_texture": gt, "n": n, "S": S, "grad_uv": np.stack([gu, gv], -1),
+           "abs_uv": np.stack([np.where(fwd["pass_u"], au, 0.0), np.where(fwd["pass_v"], av, 0.0)], -1)}
+    if shared:
+        out.update({k: out[k][0] for k in ("grad_texture", "n", "S")})
+    return out
+
+
+# ---- the table
+
+FRAMES = {"1x1": (1, 1, 1), "15x17": (1, 15, 17), "16x16": (1, 16, 16), "63x65": (1, 63, 65), "3x5x6": (3, 5, 6)}
+TEXTURES = [(1, 1), (1, 5), (5, 1), (2, 2), (5, 7), (64, 64)]
+CHANNELS = [1, 3, 4, 8]
+
+
+def _rng(*key):
+    return np.random.default_rng([sum(ord(ch) * (i + 1) for i, ch in enumerate(str(k))) for k in key])
+
+
+def _yx(shape):
+    B, H, W = shape
+    y, x = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    return np.broadcast_to(y, shape), np.broadcast_to(x, shape)
+
+
+def _uv_random(shape, Th, Tw, rng):
+    return rng.uniform(-0.3, 1.3, shape + (2,))
+
+
+def _uv_exact(shape, Th, Tw, rng):
+    """exactly 0 and 1, the texel centres (j + 0.5) / T and the texel edges j / T"""
+    def pick(T):
+        vals = np.concatenate([[0.0, 1.0], (np.arange(T) + 0.5) / T, np.arange(T + 1) / T]).astype(F32)
+        return vals[rng.integers(0, len(vals), shape)]
+    return np.stack([pick(Tw), pick(Th)], -1)
+
+
+def _uv_magnify(shape, Th, Tw, rng):
+    """a smooth warp moving 1/16 texel per pixel: a 16 x 16 tile lands in a 2 x 2 (at most 3 x 3) patch of texels"""
+    y, x = _yx(shape)
+    u = 0.31 + (x + 0.25 * np.sin(y / 5.0)) / (16.0 * Tw)
+    v = 0.47 + (y + 0.25 * np.cos(x / 7.0)) / (16.0 * Th)
+    return np.stack([u, v], -1)
+
+
+def _uv_scatter(shape, Th, Tw, rng):
+    """uniform over the texture: a tile's footprint is the whole texture"""
+    return rng.uniform(0.0, 1.0, shape + (2,))
+
+
+def _uv_seam(shape, Th, Tw, rng):
+    """every row crosses u = 1 (repeat mode: columns Tw - 1 and 0) while v sweeps about a fifth of the height"""
+    y, x = _yx(shape)
+    W, H = shape[2], shape[1]
+    return np.stack([0.96 + 0.08 * (x + 0.3) / W, 0.4 + 0.2 * (y + 0.6) / H], -1)
+
+
+def _uv_extreme(shape, Th, Tw, rng):
+    uv = rng.uniform(-0.3, 1.3, shape + (2,)).astype(F32)
+    special = np.array([1000.25, -1e-30, 3e38, -1000.75, 1.0, -0.0], F32)
+    uv[..., 0] = special[rng.integers(0, len(special), shape)]
+    flat = uv.reshape(-1, 2)
+    flat[: min(len(special), len(flat)), 1] = special[: min(len(special), len(flat))]
+    return uv
+
+
+UV_FAMILIES = {"random": _uv_random, "exact": _uv_exact, "magnify16": _uv_magnify, "scatter": _uv_scatter,
+               "seam": _uv_seam, "extreme": _uv_extreme}
+
+
+def _background(ident, shape):
+    """the sampled pixels of a frame (True = covered): one of deferred_cases.frames()' layouts, picked by the case's
+    name; the three-frame batch alternates between its leak pattern and a layout per frame"""
+    B, H, W = shape
+    names = sorted(set(deferred_cases.LAYOUTS) - {"all_background"})  # (the leak batch has the all-background frames)
+    k = sum(ord(ch) for ch in ident)
+    if B == 3 and k % 2 == 0:
+        return dict(deferred_cases.FRAMES)["3x5x6-leak"]
+    return np.stack([deferred_cases.LAYOUTS[names[(k + b) % len(names)]](H, W) for b in range(B)])
+
+
+# (id, frame, texture size, C, per-frame texture, uv family, wrap, holes)
+# holes: None = every pixel finite; "bg" = -inf background (+ one NaN and one +inf in a single channel); "mask" = an
+# explicit mask that disagrees with finiteness where the uv is finite (and the -inf background besides)
+def _table():
+    rows = []
+
+    def add(frame, tex, C, per_frame, family, wrap, holes=None):
+        ident = "%s-t%dx%d-c%d-%s-%s-%s%s" % (frame, tex[0], tex[1], C, "perframe" if per_frame else "shared", family,
+                                               wrap, "-" + holes if holes else "")
+        rows.append((ident, frame, tex, C, per_frame, family, wrap, holes))
+
+    # every frame x every texture size, random uv, the channel count and the form cycling, both wraps
+    k = 0
+    for frame in FRAMES:
+        for tex in TEXTURES:
+            add(frame, tex, CHANNELS[k % 4], (k // 2) % 2 == 1, "random", WRAPS[k % 2], ("bg", None, "mask")[k % 3])
+            k += 1
+    # every channel count, both forms, on the frame with several tiles and the batch
+    for C in CHANNELS:
+        for per_frame in (False, True):
+            add("63x65", (5, 7), C, per_frame, "random", "clamp", "bg")
+            add("3x5x6", (5, 7), C, per_frame, "random", "repeat", "mask")
+    # exact coordinates: 0, 1, centres and edges
+    for tex in TEXTURES:
+        add("15x17", tex, 3, False, "exact", "clamp")
+        add("15x17", tex, 3, False, "exact", "repeat")
+    # 16x magnification (a tile in a 2x2 patch), scattered (no patch fits), the repeat seam, extreme u
+    for frame in ("16x16", "63x65"):
+        add(frame, (64, 64), 3, False, "magnify16", "clamp", "bg")
+        add(frame, (64, 64), 8, False, "scatter", "clamp")
+        add(frame, (64, 64), 4, False, "seam", "repeat")
+        add(frame, (5, 7), 1, False, "seam", "repeat")
+    add("3x5x6", (64, 64), 3, True, "scatter", "repeat", "mask")
+    add("3x5x6", (64, 64), 3, True, "magnify16", "repeat", "bg")
+    for tex in ((5, 7), (64, 64), (1, 1)):
+        add("15x17", tex, 3, False, "extreme", "repeat")
+    add("15x17", (5, 7), 3, False, "extreme", "clamp", "bg")
+    return rows
+
+
+TABLE = _table()
+CASE_IDS = [r[0] for r in TABLE]
+assert len(set(CASE_IDS)) == len(CASE_IDS)
+_ROWS = {r[0]: r for r in TABLE}
+
+
+@functools.lru_cache(maxsize=None)
+def case_input(ident):
+    """(texture float32, uv float32 [B,H,W,2], mask uint8 [B,H,W] or None, wrap, grad float32 [B,H,W,C])"""
+    _, frame, (Th, Tw), C, per_frame, family, wrap, holes = _ROWS[ident]
+    shape = FRAMES[frame]
+    rng = _rng(ident)
+    texture = rng.standard_normal(((shape[0],) if per_frame else ()) + (Th, Tw, C)).astype(F32)
+    uv = np.ascontiguousarray(UV_FAMILIES[family](shape, Th, Tw, rng), F32)
+    mask = None
+    if holes:
+        covered = _background(ident, shape)
+        uv[~covered] = -np.inf
+        flat = uv.reshape(-1, 2)
+        if len(flat) >= 4:  # a NaN and a +inf in one channel only
+            flat[1, 0] = np.nan
+            flat[len(flat) // 2, 1] = np.inf
+        if holes == "mask":
+            finite = np.isfinite(uv).all(-1)
+            mask = (finite & (rng.random(shape) < 0.6)).astype(np.uint8)
+            assert finite.sum() < 16 or (finite & (mask == 0)).any()  # (the mask says no where the uv is finite)
+    grad = rng.standard_normal(shape + (C,)).astype(F32)
+    return texture, uv, mask, wrap, grad
+
+
+@functools.lru_cache(maxsize=None)
+def case(ident):
+    """(inputs, forward dict, vjp dict) of the float32 statement: computed once per process, treat as read-only"""
+    texture, uv, mask, wrap, grad = case_input(ident)
+    fwd = sample(texture, uv, mask, wrap)
+    return (texture, uv, mask, wrap, grad), fwd, sample_vjp(texture, grad, fwd)
+
+
+# ---- the exact scatter: weights in {0, 1/4, 1/2, 1} and small integer cotangents, so that every partial sum of the
+# texture gradient is exact in float32 and the result does not depend on the order of the atomics
+
+@functools.lru_cache(maxsize=None)
+def exact_scatter_case(kind, C=3, frames=1):
+    """kind 'magnify16': half-texel steps every 8 pixels (16 pixels per texel: the LDS patch); 'scatter': random
+    half-texel positions over the 64 x 64 texture (direct atomics).  -> (inputs, forward dict, vjp dict)"""
+    shape, T = (frames, 63, 65), 64
+    rng = _rng("exact", kind, C, frames)
+    if kind == "magnify16":
+        y, x = _yx(shape)
+        ku, kv = 37 + (x // 8).astype(np.int64), 51 + (y // 8).astype(np.int64)
+    else:
+        ku, kv = rng.integers(1, 2 * T, shape), rng.integers(1, 2 * T, shape)
+    uv = np.stack([ku / (2.0 * T), kv / (2.0 * T)], -1).astype(F32)  # x = k / 2 - 0.5: a in {0, 0.5}
+    uv[:, 3, 4] = -np.inf
+    texture = rng.integers(-2, 3, (T, T, C)).astype(F32)
+    grad = rng.integers(-3, 4, shape + (C,)).astype(F32)
+    fwd = sample(texture, uv, None, "clamp")
+    assert set(np.unique(fwd["a"])) <= {0.0, 0.5} and set(np.unique(fwd["b"])) <= {0.0, 0.5}
+    return (texture, uv, None, "clamp", grad), fwd, sample_vjp(texture, grad, fwd)
+
+
+# ---- bounds.  One term of grad_texture, g * w1 * w2 with the float32 weights the statement hands over, is two
+# float32 products: k = 2 roundings.  n terms are summed by n - 1 additions whatever their grouping (LDS patch first
+# or not), each rounding a partial sum of at most S(1 + O(2^-24)); the n-th unit absorbs the second-order terms.
+K_TEXTURE = 2
+
+
+def texture_bound(vjp):
+    return (vjp["n"] + K_TEXTURE) * 2.0 ** -24 * vjp["S"]
+
+
+def uv_roundings(C):
+    """One channel's term of grad_u, Tw * g * ((t01 - t00) * (1 - b) + (t11 - t10) * b), passes through at most five
+    float32 roundings on any path: the texel difference, its product with the weight, the sum of the two products,
+    the product with g, the final product with Tw.  grad_v's, Th * g * (bot - top), likewise: the product t * w, the
+    sum inside top (or bot), the difference, the product with g, the product with Th.  The C terms are summed by
+    C - 1 additions, and one more unit absorbs the second-order terms: k = 5 + (C - 1) + 1."""
+    return C + 5
+
+
+def uv_bound(vjp, C):
+    return uv_roundings(C) * 2.0 ** -24 * vjp["abs_uv"]
