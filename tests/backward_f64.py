@@ -21,7 +21,10 @@ own terms, and shares no code or algebra with either --
   * colours: dL/dc_v += lambda_v(p) G(p) at the pixel centre of every covered pixel; dL/dbackground = G on
     uncovered pixels.
 The visible record of each pixel (the forward's g-buffer) is an input: visibility is the forward's output,
-pinned separately (tests/exact_cover.py, bit-exact GPU vs oracle).  Pure-Python loops: small frames only.
+pinned separately -- coverage by tests/exact_cover.py, depth, clipping, the visible record and the forward's
+values by tests/forward_exact.py (exact plane depth with derived float32 bounds; the oracle against it in
+tests/test_forward_exact.py, the HIP kernels in tests/test_gpu_forward_exact.py).  Pure-Python loops: small
+frames only.
 """
 import numpy as np
 
@@ -52,7 +55,8 @@ def _snap(v4, W, H, clamp=None):
 
 class Tri:
     """One rasterised (sub-)triangle: integer edge functions E_k(P) = A_k Px + B_k Py + C_k (interior
-    positive, P in 1/256 px), its vertices' clip w and their parent barycentric basis."""
+    positive, P in 1/256 px), its vertices' clip w and their parent barycentric basis.  X, Y (snapped, R2) and
+    zw (R1's window depth (z * (1 / w)) * 0.5 + 0.5 in float32) are R4's inputs, kept for tests/forward_exact.py."""
 
     def __init__(self, verts7, W, H, clamp=None):
         X, Y = zip(*(_snap(p[:4], W, H, clamp) for p in verts7))
@@ -66,6 +70,9 @@ class Tri:
         sg = 1 if D > 0 else -1
         self.A, self.B, self.C = [sg * a for a in A], [sg * b for b in B], [sg * c for c in C]
         self.D = sg * D
+        self.X, self.Y = list(X), list(Y)
+        with np.errstate(all="ignore"):
+            self.zw = [(F32(p[2]) * (F32(1.0) / F32(p[3]))) * F32(0.5) + F32(0.5) for p in verts7]
         self.w = [float(p[3]) for p in verts7]
         self.basis = [[float(p[4 + i]) for i in range(3)] for p in verts7]
 
@@ -82,6 +89,23 @@ class Tri:
                 continue
             return False
         return True
+
+    def covers_grid(self, i0, i1, j0, j1):
+        """`covers` at every pixel centre of columns i0..i1 and window rows j0..j1 (inclusive): bool [rows, columns]
+        and the three edge values there (the same integers: int64 while they fit, Python ints otherwise)."""
+        big = max(abs(x) for x in self.A + self.B) * 256 * (max(abs(i0), abs(i1), abs(j0), abs(j1)) + 1) >= 2 ** 61 \
+            or max(abs(c) for c in self.C) >= 2 ** 61
+        dt = object if big else np.int64
+        px = (np.arange(i0, i1 + 1, dtype=np.int64) * 256 + 128).astype(dt)[None, :]
+        py = (np.arange(j0, j1 + 1, dtype=np.int64) * 256 + 128).astype(dt)[:, None]
+        inside = np.ones((j1 - j0 + 1, i1 - i0 + 1), bool)
+        E = []
+        for k in range(3):
+            e = self.A[k] * px + self.B[k] * py + self.C[k]
+            owned = self.A[k] > 0 or (self.A[k] == 0 and self.B[k] < 0)
+            inside &= ((e > 0) | ((e == 0) & owned)).astype(bool)
+            E.append(e)
+        return inside, E
 
     def weights(self, E2):
         """Parent lambda_i and Wm at the point where the (doubled) edge values are E2 (sum = 2D)."""

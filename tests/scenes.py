@@ -395,3 +395,122 @@ def clipped_sliver_scene(seed, W=48, H=40, C=3, n=10):
     cols = rng.uniform(0, 1, size=(3 * nf, C)).astype(np.float32)
     bg = rng.uniform(0, 1, size=(H, W, C)).astype(np.float32)
     return bg, v, cols, faces
+
+
+def deep_scene(perspective, W=96, H=80, F=400, seed=11, dup=120, near=80):
+    """A deep stack (about 90x depth complexity at the defaults): frame-sized random triangles, the first `dup`
+    drawn again under higher face indices (exact depth ties: the lower face wins) and the next `near` copied
+    with their own vertices and z nudged by 1e-7 w (about 0.8 of a 24-bit depth quantum: near ties)."""
+    bg, v, c, f = random_triangles(F=F, W=W, H=H, radius_px=70.0, seed=seed, perspective=perspective)
+    dups = f[:dup].copy()                                  # identical planes, higher face index
+    nears = f[dup:dup + near].copy()                       # own vertices, depth nudged by ~1e-7
+    vn = v[nears.reshape(-1)].copy()
+    vn[:, 2] += np.float32(1e-7) * vn[:, 3]
+    cn = c[nears.reshape(-1)]
+    nears = (v.shape[0] + np.arange(nears.size, dtype=np.int32)).reshape(-1, 3)
+    return bg, np.concatenate([v, vn]).astype(np.float32), np.concatenate([c, cn]).astype(np.float32), \
+        np.concatenate([f, dups, nears]).astype(np.int32)
+
+
+def interpenetrating_scene(seed, W=64, H=48, C=3, perspective=False, pairs=6):
+    """Pairs of large triangles over nearly the same footprint whose depths slope in opposite directions, so
+    that the depth order of a pair flips along a line inside the frame (and inside a tile); pairs overlap
+    other pairs.  perspective: every vertex scaled by its own w in [1, 3]."""
+    rng = np.random.default_rng(seed)
+    tris = []
+    for _ in range(pairs):
+        centre = rng.uniform(-0.5, 0.5, 2)
+        ang = rng.uniform(0, 2 * np.pi) + np.array([0.0, 2.1, 4.2])
+        zmid = rng.uniform(-0.5, 0.5)
+        slope = rng.uniform(0.1, 0.4) * rng.choice([-1.0, 1.0])
+        for sign in (1.0, -1.0):
+            rad = rng.uniform(0.5, 1.1, 3)
+            xy = centre + np.stack([np.cos(ang) * rad, np.sin(ang) * rad], -1) + rng.uniform(-0.05, 0.05, (3, 2))
+            z = zmid + sign * slope * (xy[:, 0] - centre[0]) + rng.uniform(-0.02, 0.02, 3)
+            tris.append(np.concatenate([xy, z[:, None], np.ones((3, 1))], 1))
+    v = np.concatenate(tris, 0)
+    if perspective:
+        v = v * rng.uniform(1, 3, size=(len(v), 1))
+    v = v.astype(np.float32)
+    faces = np.arange(len(v), dtype=np.int32).reshape(-1, 3)
+    cols = rng.uniform(0, 1, size=(len(v), C)).astype(np.float32)
+    bg = rng.uniform(0, 1, size=(H, W, C)).astype(np.float32)
+    return bg, v, cols, faces
+
+
+def near_far_scene(seed, W=64, H=48, C=3, outside=False, n=14):
+    """Faces that cross the near (z = -w) and far (z = w) planes: per-vertex z / w in [-1.6, 1.6], w in
+    [0.5, 2].  outside = False: every vertex inside the guard band, so the faces are not clipped and R4's
+    per-pixel range test alone bounds them; outside = True: the same faces with one vertex moved along its edge
+    direction to 1.2 times the guard band, so that they take R5's clipping path (near plane clipped, far plane
+    still R4's)."""
+    rng = np.random.default_rng(seed)
+    gx = 32768.0 / W
+    tris = []
+    for _ in range(n):
+        xy = rng.uniform(-1.0, 1.0, 2) + rng.uniform(-0.9, 0.9, (3, 2))
+        zn = rng.uniform(-1.6, 1.6, 3)
+        w = rng.uniform(0.5, 2.0, 3)
+        k, side = rng.integers(3), rng.choice([-1.0, 1.0])
+        if outside:
+            xy[k, 0] = 1.2 * gx * side
+        tris.append(np.concatenate([xy * w[:, None], (zn * w)[:, None], w[:, None]], 1))
+    v = np.concatenate(tris, 0).astype(np.float32)
+    faces = np.arange(len(v), dtype=np.int32).reshape(-1, 3)
+    cols = rng.uniform(0, 1, size=(len(v), C)).astype(np.float32)
+    bg = rng.uniform(0, 1, size=(H, W, C)).astype(np.float32)
+    return bg, v, cols, faces
+
+
+def exact_tie_scene(seed, W=64, H=48, C=3, n=24, distances=(1, 2, 5, 17, 40)):
+    """Overlapping faces with exact duplicates: face i (i < len(distances) * 3) is drawn again `distances[i % ..]`
+    places later in the draw order, with the same ordered vertex triple -- through the same vertex indices or
+    (every other one) through bit-identical copies of the vertices with other colours -- so both compute
+    bit-identical depths and the lower face index must win (R4).  No rotated or reversed copies: those are
+    different ordered triples.  Returns the scene and the list of (original, duplicate) face indices."""
+    rng = np.random.default_rng(seed)
+    bg, v, c, f = random_triangles(F=n, W=W, H=H, C=C, radius_px=16.0, seed=seed, perspective=bool(seed % 2))
+    order = list(range(n))                       # entries: original face number
+    for i in range(3 * len(distances)):
+        order.insert(min(order.index(i) + distances[i % len(distances)], len(order)), i)
+    v, c, faces, pairs, first = [v], [c], [], [], {}
+    nv = v[0].shape[0]
+    for pos, i in enumerate(order):
+        if i not in first:
+            first[i] = pos
+            faces.append(f[i])
+            continue
+        pairs.append((first[i], pos))
+        if i % 2:
+            faces.append(f[i])
+        else:
+            v.append(v[0][f[i]])
+            c.append(rng.uniform(0, 1, size=(3, C)).astype(np.float32))
+            faces.append(np.arange(nv, nv + 3, dtype=np.int32))
+            nv += 3
+    return (bg, np.concatenate(v).astype(np.float32), np.concatenate(c).astype(np.float32),
+            np.array(faces, np.int32)), pairs
+
+
+FLAT_DEPTHS = (0.0, 0.25, 0.5, 1.0 - 2.0 ** -23, 1.0 - 2.0 ** -24, 1.0)
+
+
+def flat_depth_scene(W=64, H=48, C=3, seed=0):
+    """Known-answer quads of constant window depth zw = FLAT_DEPTHS[q] (z = 2 zw - 1 at w = 1, exact in float32),
+    side by side in columns of W / 6 of the frame, two faces each.  Returns the scene and the window-x range
+    [x0, x1) in pixels of every quad."""
+    rng = np.random.default_rng(seed)
+    n = len(FLAT_DEPTHS)
+    v, faces, spans = [], [], []
+    for q, zw in enumerate(FLAT_DEPTHS):
+        x0, x1 = (W * q) // n, (W * (q + 1)) // n
+        spans.append((x0, x1))
+        a, b = x0 * 2.0 / W - 1.0, x1 * 2.0 / W - 1.0
+        z = 2.0 * zw - 1.0
+        base = len(v)
+        v += [[a, -0.75, z, 1.0], [b, -0.75, z, 1.0], [b, 0.75, z, 1.0], [a, 0.75, z, 1.0]]
+        faces += [[base, base + 1, base + 2], [base, base + 2, base + 3]]
+    v = np.array(v, np.float64).astype(np.float32)
+    cols = rng.uniform(0, 1, size=(len(v), C)).astype(np.float32)
+    bg = rng.uniform(0, 1, size=(H, W, C)).astype(np.float32)
+    return (bg, v, cols, np.array(faces, np.int32)), spans

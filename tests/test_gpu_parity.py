@@ -389,16 +389,7 @@ def test_deep_depth_complexity_culling(perspective):
     check_scene(bg, v2, c2, f2)
 
 
-def _deep_scene(perspective, W=96, H=80, F=400, seed=11):
-    bg, v, c, f = scenes.random_triangles(F=F, W=W, H=H, radius_px=70.0, seed=seed, perspective=perspective)
-    dup = f[:120].copy()                                   # identical planes, higher face index
-    near = f[120:200].copy()                               # own vertices, depth nudged by ~1e-7
-    vn = v[near.reshape(-1)].copy()
-    vn[:, 2] += np.float32(1e-7) * vn[:, 3]
-    near = (v.shape[0] + np.arange(near.size, dtype=np.int32)).reshape(-1, 3)
-    cn = c[f[120:200].reshape(-1)]
-    return bg, np.concatenate([v, vn]).astype(np.float32), np.concatenate([c, cn]).astype(np.float32), \
-        np.concatenate([f, dup, near]).astype(np.int32)
+_deep_scene = scenes.deep_scene
 
 
 @pytest.mark.parametrize("scene", ["deep_affine", "deep_perspective", "r64_1024", "c3_seed0"])
