@@ -9,13 +9,16 @@
 //                      record) pairs in LDS, reserves its range of every touched coarse-tile slab with one
 //                      returning device atomic per (workgroup, tile) and writes the 8-B bin entries there.
 //                      Filler workgroups past the faces zero the caller's gradient accumulators.
-//   K4 raster_kernel   (raster_kernel.h) one 256-thread workgroup per 16x16 tile (a wave per 8x8 block):
-//                      reads its coarse slab once, stages the tile's survivors in LDS with tile-relative
-//                      32-bit edge values (exact), each lane owns one pixel and keeps the min
-//                      (depth24<<32 | face) key over its wave's entry list (long lists depth-culled), then
-//                      resolves in-kernel: perspective-correct Gouraud colour (R6) or background, coalesced
-//                      [B,H,W,C] writes + the int32 g-buffer + neighbour-coverage bits.  This fuses the
-//                      reference's upload_background + raster + second pass + download_pixels
+//   K4 raster_kernel   (raster_kernel.h) one 256-thread workgroup per 16x16 tile (a wave per 8x8 block), in
+//                      phases: fused_frame_setup (small scenes: no K1, the frame's records set up in LDS);
+//                      first loads + launch_housekeeping (parity publish, deep-cull report, zero-fill of the
+//                      gradient accumulators); the visibility pass -- bin filter of the coarse slab,
+//                      stage_round (survivors into LDS with tile-relative exact 32-bit edge values),
+//                      build_wave_list and the list walk, each lane keeping the min (depth24<<32 | face) key
+//                      of its pixel (long lists depth-culled); resolve_record; write_uncovered (background) or
+//                      the barycentrics (R6), write_gbuf_outputs, and shade_gouraud / a procedural program:
+//                      coalesced [B,H,W,C] writes + the int32 g-buffer + neighbour-coverage bits.  This fuses
+//                      the reference's upload_background + raster + second pass + download_pixels
 //                      (csrc/rasterise_egl.cu:16-129, rasterise_egl.cpp:370-503) into one HBM pass.
 //   K5 grad_kernel     (grad_kernel.h) backward: dL/dbackground, dL/dvertex_colors and the
 //                      filter-based dL/dvertices (README.md:146-147) for the gradient contract of
@@ -25,7 +28,8 @@
 // three kernels live in the headers named above, included into this one translation unit, each followed by its
 // typed launcher (launch_setup / launch_raster / launch_grad): the one function that writes the kernel's <<<>>> and
 // knows its parameter order.  The entry points here fill a RasterLaunch / GradLaunch by field name, pick the channel
-// specialisation with with_channels() and the variant with an if-chain of launcher calls.
+// specialisation with with_channels() and the variant with an if-chain of launcher calls, the raster's by named
+// mode flags (launch_raster<CC, kRasterFused | kRasterGbuf>(a)).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -231,6 +235,23 @@ void with_channels(int C, Fn &&fn)
     else fn(std::integral_constant<int, 0>{});
 }
 
+// Every channel count its own specialisation (the deferred per-pixel ops: dilation, texture sampling): calls
+// fn(std::integral_constant<int, C>{}) for the run-time C in 1..DIRT_MAX_CHANNELS, which the callers have validated.
+template <class Fn>
+void with_each_channel_count(int C, Fn &&fn)
+{
+    switch (C) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    case 5: fn(std::integral_constant<int, 5>{}); break;
+    case 6: fn(std::integral_constant<int, 6>{}); break;
+    case 7: fn(std::integral_constant<int, 7>{}); break;
+    default: fn(std::integral_constant<int, 8>{}); break;
+    }
+}
+
 // Start / stop events of a timed debug entry point, released on every path out of it.  (ProfScope's events outlive
 // their scope on purpose: dirt_profile_read reads them later.)
 struct EventPair {
@@ -276,14 +297,8 @@ __global__ __launch_bounds__(256) void zero2_kernel(float *__restrict__ a, int64
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // 16-B stores over a 16-B aligned buffer (torch allocations), scalar stores otherwise; then the tail
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int64_t na4 = (reinterpret_cast<uintptr_t>(a) & 15) == 0 ? na / 4 : 0;
-    const int64_t nb4 = (reinterpret_cast<uintptr_t>(b) & 15) == 0 ? nb / 4 : 0;
-    for (int64_t k = gid; k < na4; k += stride) reinterpret_cast<float4 *>(a)[k] = z;
-    for (int64_t k = na4 * 4 + gid; k < na; k += stride) a[k] = 0.0f;
-    for (int64_t k = gid; k < nb4; k += stride) reinterpret_cast<float4 *>(b)[k] = z;
-    for (int64_t k = nb4 * 4 + gid; k < nb; k += stride) b[k] = 0.0f;
+    zero_strided(a, na, gid, stride);
+    zero_strided(b, nb, gid, stride);
 }
 
 // PMC calibration (tools/pmc_calibrate.py): read `n` elements of W bytes once each, coalesced, with the
@@ -590,28 +605,28 @@ static int rasterise_fwd_impl(const float *background, int tcb, const float *ver
     a.zero_a = zero_grad_vertices; a.zero_b = zero_grad_vertex_colors;
     a.verts = vertices; a.cam = camera_pos; a.sid = shader_id; a.tcb = tcb;
     with_channels(C, [&](auto cc) {
-        constexpr int CC = decltype(cc)::value, G = DIRT_SHADER_GOURAUD;
+        constexpr int CC = decltype(cc)::value;
         if (shader_id == DIRT_SHADER_OCEANIC_HORIZON) launch_raster<CC, 0, DIRT_SHADER_OCEANIC_HORIZON>(a);
         else if (shader_id == DIRT_SHADER_HILL) launch_raster<CC, 0, DIRT_SHADER_HILL>(a);
         else if (shader_id >= DIRT_SHADER_OCEANIC) launch_raster<CC, 0, DIRT_SHADER_OCEANIC>(a);
         else if (nopix && fused) {
             a.gbo = gbo; a.faces = faces; a.stash_hdr = stash_hdr;
-            launch_raster<CC, 0, G, false, /*FUSED=*/true, /*NOPIX=*/true>(a);
+            launch_raster<CC, kRasterFused | kRasterNoPix>(a);
         } else if (nopix) {
             a.gbo = gbo; a.stash_hdr = stash_hdr;
-            launch_raster<CC, 0, G, false, false, /*NOPIX=*/true>(a);
+            launch_raster<CC, kRasterNoPix>(a);
         } else if (deep && !fused && !want_gb) {
             a.dga = dga;
-            launch_raster<CC, 0, G, false, false, false, /*OCC=*/true>(a);
+            launch_raster<CC, kRasterOcc>(a);
         } else if (fused && want_gb) {
             a.gbo = gbo; a.faces = faces;
-            launch_raster<CC, 0, G, /*GB=*/true, /*FUSED=*/true>(a);
+            launch_raster<CC, kRasterFused | kRasterGbuf>(a);
         } else if (fused) {
             a.gbo = gbo; a.faces = faces;
-            launch_raster<CC, 0, G, false, /*FUSED=*/true>(a);
+            launch_raster<CC, kRasterFused>(a);
         } else if (want_gb) {
             a.gbo = gbo;
-            launch_raster<CC, 0, G, /*GB=*/true>(a);
+            launch_raster<CC, kRasterGbuf>(a);
         } else {
             a.dga = dga;
             launch_raster<CC>(a);
@@ -671,7 +686,7 @@ int dirt_rasterise_fwd_resolve(const float *background, const float *vertex_colo
     a.recs = sv.recs; a.fdata = sv.fdata; a.gb_in = gbuffer_in;
     a.zero_a = zero_grad_vertices; a.zero_b = zero_grad_vertex_colors;
     with_channels(C, [&](auto cc) {
-        launch_raster<decltype(cc)::value, 0, DIRT_SHADER_GOURAUD, false, false, false, false, /*RESOLVE=*/true>(a);
+        launch_raster<decltype(cc)::value, kRasterResolve>(a);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
@@ -1025,13 +1040,14 @@ int dirt_debug_raster_variant(int variant, const float *background, const float 
     a.counts = sc.ccount; a.flag = sc.flag; a.bins = sc.bins; a.slab = L.slab;
     EventPair ev;
     HIP_TRY(ev.start(stream));
+    constexpr int G = DIRT_SHADER_GOURAUD;  // (the ablation mask AB is the launcher's last parameter)
     switch (variant) {
-    case 0: launch_raster<3, 0>(a); break;        case 1: launch_raster<3, 1>(a); break;
-    case 2: launch_raster<3, 2>(a); break;        case 4: launch_raster<3, 4>(a); break;
-    case 8: launch_raster<3, 8>(a); break;        case 32: launch_raster<3, 32>(a); break;
-    case 64: launch_raster<3, 64>(a); break;      case 96: launch_raster<3, 96>(a); break;
-    case 128: launch_raster<3, 128>(a); break;    case 512: launch_raster<3, 512>(a); break;
-    case 1024: launch_raster<3, 1024>(a); break;  case 2048: launch_raster<3, 2048>(a); break;
+    case 0: launch_raster<3, 0, G, 0>(a); break;        case 1: launch_raster<3, 0, G, 1>(a); break;
+    case 2: launch_raster<3, 0, G, 2>(a); break;        case 4: launch_raster<3, 0, G, 4>(a); break;
+    case 8: launch_raster<3, 0, G, 8>(a); break;        case 32: launch_raster<3, 0, G, 32>(a); break;
+    case 64: launch_raster<3, 0, G, 64>(a); break;      case 96: launch_raster<3, 0, G, 96>(a); break;
+    case 128: launch_raster<3, 0, G, 128>(a); break;    case 512: launch_raster<3, 0, G, 512>(a); break;
+    case 1024: launch_raster<3, 0, G, 1024>(a); break;  case 2048: launch_raster<3, 0, G, 2048>(a); break;
     default:
         return fail(DIRT_EINVAL, "dirt_debug_raster_variant: unknown variant");
     }
@@ -1448,16 +1464,9 @@ int dirt_dilate_fwd(const float *x, const uint8_t *mask, int B, int H, int W, in
     if (rc || n == 0) return rc;
     if (!x || !out || !route) return fail(DIRT_EINVAL, "dilate: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    switch (C) {
-    case 1: launch_dilate_fwd<1>(x, mask, H, W, n, out, route, stream); break;
-    case 2: launch_dilate_fwd<2>(x, mask, H, W, n, out, route, stream); break;
-    case 3: launch_dilate_fwd<3>(x, mask, H, W, n, out, route, stream); break;
-    case 4: launch_dilate_fwd<4>(x, mask, H, W, n, out, route, stream); break;
-    case 5: launch_dilate_fwd<5>(x, mask, H, W, n, out, route, stream); break;
-    case 6: launch_dilate_fwd<6>(x, mask, H, W, n, out, route, stream); break;
-    case 7: launch_dilate_fwd<7>(x, mask, H, W, n, out, route, stream); break;
-    default: launch_dilate_fwd<8>(x, mask, H, W, n, out, route, stream); break;
-    }
+    with_each_channel_count(C, [&](auto c) {
+        launch_dilate_fwd<decltype(c)::value>(x, mask, H, W, n, out, route, stream);
+    });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }
@@ -1470,16 +1479,9 @@ int dirt_dilate_bwd(const float *grad_out, const uint32_t *route, int B, int H, 
     if (rc || n == 0) return rc;
     if (!grad_out || !route || !grad_x) return fail(DIRT_EINVAL, "dilate: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    switch (C) {
-    case 1: launch_dilate_bwd<1>(grad_out, route, H, W, n, grad_x, stream); break;
-    case 2: launch_dilate_bwd<2>(grad_out, route, H, W, n, grad_x, stream); break;
-    case 3: launch_dilate_bwd<3>(grad_out, route, H, W, n, grad_x, stream); break;
-    case 4: launch_dilate_bwd<4>(grad_out, route, H, W, n, grad_x, stream); break;
-    case 5: launch_dilate_bwd<5>(grad_out, route, H, W, n, grad_x, stream); break;
-    case 6: launch_dilate_bwd<6>(grad_out, route, H, W, n, grad_x, stream); break;
-    case 7: launch_dilate_bwd<7>(grad_out, route, H, W, n, grad_x, stream); break;
-    default: launch_dilate_bwd<8>(grad_out, route, H, W, n, grad_x, stream); break;
-    }
+    with_each_channel_count(C, [&](auto c) {
+        launch_dilate_bwd<decltype(c)::value>(grad_out, route, H, W, n, grad_x, stream);
+    });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }
@@ -1550,22 +1552,6 @@ int texture_sizes(int texture_frames, int Th, int Tw, int B, int H, int W, int C
     return DIRT_OK;
 }
 
-// fn(std::integral_constant<int, C>{}) for the run-time channel count C in 1..DIRT_MAX_CHANNELS
-template <class Fn>
-void texture_channels(int C, Fn &&fn)
-{
-    switch (C) {
-    case 1: fn(std::integral_constant<int, 1>{}); break;
-    case 2: fn(std::integral_constant<int, 2>{}); break;
-    case 3: fn(std::integral_constant<int, 3>{}); break;
-    case 4: fn(std::integral_constant<int, 4>{}); break;
-    case 5: fn(std::integral_constant<int, 5>{}); break;
-    case 6: fn(std::integral_constant<int, 6>{}); break;
-    case 7: fn(std::integral_constant<int, 7>{}); break;
-    default: fn(std::integral_constant<int, 8>{}); break;
-    }
-}
-
 template <int C>
 void launch_texture_fwd(const float *texture, int64_t frame_stride, int Th, int Tw, const float *uv,
                         const uint8_t *mask, int64_t hw, int64_t n, int wrap, float *texels, uint8_t *valid,
@@ -1599,7 +1585,7 @@ int dirt_texture_sample_fwd(const float *texture, int texture_frames, int Th, in
     if (!texture || !uv || !texels || !valid) return fail(DIRT_EINVAL, "texture_sample: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int64_t fs = texture_frames == 1 ? 0 : (int64_t)Th * Tw * C, hw = (int64_t)H * W;
-    texture_channels(C, [&](auto c) {
+    with_each_channel_count(C, [&](auto c) {
         launch_texture_fwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, hw, n, wrap, texels, valid, stream);
     });
     HIP_TRY(hipGetLastError());
@@ -1618,7 +1604,7 @@ int dirt_texture_sample_bwd(const float *texture, int texture_frames, int Th, in
     const int64_t fs = texture_frames == 1 ? 0 : (int64_t)Th * Tw * C;
     if (grad_texture)
         HIP_TRY(hipMemsetAsync(grad_texture, 0, (size_t)texture_frames * Th * Tw * C * sizeof(float), stream));
-    texture_channels(C, [&](auto c) {
+    with_each_channel_count(C, [&](auto c) {
         launch_texture_bwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, B, H, W, wrap, grad_texels, grad_texture,
                                                grad_uv, stream);
     });

@@ -15,6 +15,8 @@
 //      |A|, |B| < 2^15; larger ones use per-lane int64, flagged), two FMAs of depth and a branch-free
 //      min of the 64-bit (depth24 << 32 | face << 3 | s) key.
 // Results are bit-identical to R3/R4 (oracle) by construction.
+// The kernel (at the end of this file) reads as a sequence of phases -- frame setup (FUSED), first loads and
+// housekeeping, the visibility pass (a-c), resolve and shade; most are functions defined just above it.
 
 constexpr int kStrips = 4;
 // The pixels a wave owns inside its 16x16 tile: an 8x8 block.  A block is a more compact shape than a 16x4 strip:
@@ -507,6 +509,231 @@ struct DeepArgs {
     uint32_t gen, prev_gen, slot;
 };
 
+// ---- The kernel's phases, in the order raster_kernel runs them.  The ones below are functions: they take values,
+// and extracting them left every instantiation's registers, spills and LDS as they were (tools/asm_diff.py,
+// profiles/r08/raster_phases).  The chunk filter, the list walk and the record's barycentrics stay inline in the
+// kernel under banner comments: as functions they changed the register allocation (same place).
+// The kernel's template parameters travel to a phase as one type.
+template <int CC_, int AB_, int SH_, bool GB_, bool FUSED_, bool NOPIX_, bool OCC_, bool RESOLVE_>
+struct RasterMode {
+    static constexpr int CC = CC_, AB = AB_, SH = SH_;
+    static constexpr bool GB = GB_, FUSED = FUSED_, NOPIX = NOPIX_, OCC = OCC_, RESOLVE = RESOLVE_;
+    static constexpr bool kNoDepth = SH_ == DIRT_SHADER_HILL;
+    static constexpr int CM = CC_ > 0 ? CC_ : DIRT_MAX_CHANNELS;  // channels the unrolled loops cover
+};
+
+// FUSED: every workgroup sets up all faces of its frame into LDS, one face per thread; the workgroup of tile 0
+// publishes them for the backward
+__device__ __forceinline__ void fused_frame_setup(Rec *s_recs, FaceData *s_fd, int b, const float *verts,
+                                                  const int32_t *faces, int V, int F, int W, int H, uint32_t *flag,
+                                                  const Rec *recs, const FaceData *fdata, int64_t nrec)
+{
+    const int t = threadIdx.x;
+    if (t < F) {
+        bool oob;
+        // (only the workgroup of tile 0 counts the R5 deviations: every workgroup repeats the frame's setup)
+        s_fd[t] = setup_face_into(verts + (int64_t)b * V * 4, faces + ((int64_t)b * F + t) * 3, V, F, W, H, t, s_recs, oob,
+                                  blockIdx.x == 0 ? flag : nullptr);
+        if (oob) atomicOr(flag, 1u);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        // publish the frame's records and FaceData for the backward (plain stores; the backward is a
+        // later launch)
+        Rec *gr = const_cast<Rec *>(recs) + (int64_t)b * nrec;
+        for (int k = t; k < (int)nrec; k += 256) {
+            const int f = face_of_record(k, F);
+            const int s = k < F ? 0 : (k - F) - (f * kExtraPerFace) + 1;
+            if (k < F || s < s_fd[f].nsub) gr[k] = s_recs[k];
+        }
+        if (t < F) const_cast<FaceData *>(fdata)[(int64_t)b * F + t] = s_fd[t];
+    }
+}
+
+// What one launch does in passing, by its first thread or spread over all workgroups: the Q-parity publish, the
+// report and clear of the automatic deep culling, and the zero-fill of the caller's gradient accumulators.
+template <class M>
+__device__ __forceinline__ void launch_housekeeping(uint32_t *flag, const DeepArgs dga, float *zero_a, int64_t nzero_a,
+                                                    float *zero_b, int64_t nzero_b)
+{
+    constexpr int AB = M::AB;
+    const int t = threadIdx.x;
+    if (!M::FUSED && !M::RESOLVE && blockIdx.x == 0 && blockIdx.y == 0 && t == 0 && !(AB & 16))
+        flag[kParQ] = (flag[kParP] & 1u) ^ 1u;
+    if (dga.host != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
+        // automatic deep culling: report whether the previous launch on this scratch was deep (to the host-mapped
+        // word the host reads when it picks the next launch's instantiation), then clear its count slot
+        uint32_t *prev = &flag[kDeepCnt + 4 * (dga.slot ^ 1u)];
+        const uint32_t sampled = gridDim.y * ((gridDim.x + kDeepSample - 1) / kDeepSample);
+        if (dga.prev_gen != 0u && *prev >= max(1u, sampled / kDeepFrac))
+            __hip_atomic_store(dga.host, dga.prev_gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        *prev = 0u;
+    }
+    if (!(AB & 16)) {
+        // housekeeping spread over all blocks (a few KB each): zero-fill the caller's gradient
+        // accumulators if it passed them (after the slab loads are in flight)
+        const int64_t nblk = (int64_t)gridDim.x * gridDim.y;
+        const int64_t gt = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x, gs = nblk * 256;
+        if (zero_a) zero_strided(zero_a, nzero_a, gt, gs);
+        if (zero_b) zero_strided(zero_b, nzero_b, gt, gs);
+    }
+}
+
+// The record visible at the pixel, -1 for none: from the visibility pass's key, or (RESOLVE) from the g-buffer word
+// of the forward this render shares its geometry with
+template <class M>
+__device__ __forceinline__ int32_t resolve_record(uint64_t best, const int32_t *gb_in, int64_t o, int F)
+{
+    if constexpr (M::RESOLVE) {
+        const int32_t g = gb_in[o];
+        return g >= 0 ? (g & kGbufIndexMask) : -1;
+    } else {
+        return best != kKeyInit<M::kNoDepth> ? key_rec(key_low<M::kNoDepth>(best), F) : -1;
+    }
+}
+
+// One staging round's entry of thread t = g - from: survivor g of the tile's n_list (`pre`: the prefix sums of the
+// four waves' segment lengths), staged into *ent_t with its mask of coverable blocks (bit 4: large) in *mask_t
+__device__ __forceinline__ void stage_round(int g, int n_list, const int (&pre)[kStrips + 1],
+                                            const int32_t (*t_list)[kFilterBlock], const Rec *frame_recs, int ti0, int tj0,
+                                            int F, StripEntry *ent_t, uint8_t *mask_t)
+{
+    uint32_t m = 0;
+    if (g < n_list) {
+        int w = 0;
+#pragma unroll
+        for (int q = 1; q < kStrips; ++q) w += g >= pre[q] ? 1 : 0;
+        const int32_t ri = t_list[w][g - pre[w]];
+        StripEntry E;
+        bool large;
+        m = stage_tile(frame_recs, ri, ti0, tj0, F, E, large);
+        int4 *d = reinterpret_cast<int4 *>(ent_t);
+        d[0] = make_int4(E.e[0], E.e[1], E.e[2], (int)E.ab[0]);
+        d[1] = make_int4((int)E.ab[1], (int)E.ab[2], __float_as_int(E.za), __float_as_int(E.zb));
+        d[2] = make_int4(__float_as_int(E.fx0), __float_as_int(E.fy0), (int)E.key, __float_as_int(E.z0));
+        m |= large ? 16u : 0u;
+    }
+    *mask_t = (uint8_t)m;
+}
+
+// This wave's entries of a staging round (nst staged, masks in t_mask) as a list in `wl` (ballot compaction of the
+// round's masks): the walk then reads offsets two at a time instead of scanning a bit mask on the scalar unit.
+// Byte offsets into t_ent of the small entries from the front, padded with the sentinel's; indices of the large
+// ones from the back.
+struct WaveList {
+    int ns, nl;  // small, large entries
+};
+__device__ __forceinline__ WaveList build_wave_list(const uint8_t *t_mask, uint32_t *wl, int nst, int wave, int lane)
+{
+    int ns = 0, nl = 0;
+    for (int c0 = 0; c0 < nst; c0 += 64) {
+        const uint32_t mm = c0 + lane < nst ? t_mask[c0 + lane] : 0u;
+        const bool mine = (mm >> wave) & 1u, big = (mm >> 4) & 1u;
+        const uint64_t bs = __ballot(mine && !big), bl = __ballot(mine && big);
+        if (mine && !big) wl[ns + lane_rank(bs)] = (uint32_t)(c0 + lane) * sizeof(StripEntry);
+        if (mine && big) wl[kWaveList - 1 - (nl + lane_rank(bl))] = (uint32_t)(c0 + lane);
+        ns += __popcll(bs);
+        nl += __popcll(bl);
+    }
+    if (lane == 0) wl[ns] = 256u * sizeof(StripEntry);  // pad / sentinel
+    return WaveList{ns, nl};
+}
+
+// A pixel no face covers: the background (hill: zero; `bg`: the pixel's own), an empty g-buffer word, cleared
+// deferred-shading outputs
+template <class M>
+__device__ __forceinline__ void write_uncovered(int64_t o, int C, const float *bg, float *out, int32_t *gbuffer,
+                                                uint8_t *covbits, const GbufOut gbo)
+{
+    constexpr int AB = M::AB;
+    gbuffer[o] = -1;
+    if constexpr (M::GB) {
+        if (gbo.depth) gbo.depth[o] = 1.0f;
+        if (gbo.bary) {
+            gbo.bary[o * 3] = 0.0f;
+            gbo.bary[o * 3 + 1] = 0.0f;
+            gbo.bary[o * 3 + 2] = 0.0f;
+        }
+        if (gbo.face) gbo.face[o] = -1;
+    }
+    if constexpr (M::SH == DIRT_SHADER_GOURAUD && !M::RESOLVE) covbits[o] = 0;
+    if constexpr (!M::NOPIX) {
+#pragma unroll
+        for (int c2 = 0; c2 < M::CM; ++c2)
+            if (c2 < C) out[c2] = M::kNoDepth ? 0.0f : bg[c2];  // (hill: no background copy)
+    }
+    PHASE_TS(4);
+    PHASE_TS(5);
+}
+
+// The deferred-shading outputs of a covered pixel (GB; every pointer may be null)
+__device__ __forceinline__ void write_gbuf_outputs(const GbufOut gbo, int64_t o, uint64_t best, const float lam[3], int face)
+{
+    if (gbo.depth) gbo.depth[o] = (float)(uint32_t)(best >> 32) / 16777215.0f;
+    if (gbo.bary) {
+        gbo.bary[o * 3] = lam[0];
+        gbo.bary[o * 3 + 1] = lam[1];
+        gbo.bary[o * 3 + 2] = lam[2];
+    }
+    if (gbo.face) gbo.face[o] = face;
+}
+
+// The procedural programs' texCoordV = perspective-correct clip xy of the pixel (shaders.cpp:19,21 alias texCoord
+// to position); `vb`: the frame's clip vertices
+__device__ __forceinline__ float2 tex_coord_v(const float *vb, const FaceData &fd, const float lam[3])
+{
+    const float *p0 = vb + (int64_t)fd.v[0] * 4, *p1 = vb + (int64_t)fd.v[1] * 4, *p2 = vb + (int64_t)fd.v[2] * 4;
+    return make_float2((lam[0] * p0[0] + lam[1] * p1[0]) + lam[2] * p2[0],
+                       (lam[0] * p0[1] + lam[1] * p1[1]) + lam[2] * p2[1]);
+}
+
+// The oceanic programs' jitter: the background texel at (texCoordV + 1) / 2 (NEAREST) = (u, v), channels x, y
+// (C = 1 broadcast)
+__device__ __forceinline__ float2 jitter_texel(const float *background, int b, int H, int W, int C, float u, float v)
+{
+    int ix = (int)floorf(u * (float)W), iy = (int)floorf(v * (float)H);
+    if (!(u * (float)W >= 0.0f)) ix = 0;
+    if (!(v * (float)H >= 0.0f)) iy = 0;
+    ix = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix);
+    iy = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy);
+    const float *texel = background + (((int64_t)b * H + (H - 1 - iy)) * W + ix) * C;
+    return make_float2(texel[0], C >= 2 ? texel[1] : texel[0]);
+}
+
+// A covered Gouraud pixel: the interpolated vertex colours (NOPIX: none), then the neighbour-coverage bits
+// (RESOLVE: left alone).  E, lam, resolve_small: the record's edge values, barycentrics and int32-path flag.
+template <class M>
+__device__ __forceinline__ void shade_gouraud(int b, const Rec *frame_recs, const FaceData *fdata_frame,
+                                              const float *colors, int V, int C, int F, const FaceData &fd,
+                                              const RasterPart &rp, const int64_t E[3], const float lam[3],
+                                              bool resolve_small, int32_t best_rec, int i, int j, int64_t o, float *out,
+                                              uint8_t *covbits, const uint32_t *flag)
+{
+    constexpr int AB = M::AB;
+    if constexpr (M::NOPIX) {
+        // (coverage only: the caller holds the pixels)
+    } else if (AB & 64) {
+        for (int k = 0; k < C; ++k) out[k] = lam[k % 3];
+    } else {
+        const float *cb = colors + (int64_t)b * V * C;
+        if (AB & 1024) {
+            // ablation: one extra dependent global round trip between the FaceData and the colour loads
+            uint32_t z0, z1;
+            asm volatile("v_mov_b32 %0, 0" : "=v"(z0) : "v"(fd.v[0]));
+            const uint32_t w = flag[kParQ + z0];
+            asm volatile("v_mov_b32 %0, 0" : "=v"(z1) : "v"(w));
+            cb += z1;
+        }
+        const float *c0 = cb + (int64_t)fd.v[0] * C, *c1 = cb + (int64_t)fd.v[1] * C, *c2 = cb + (int64_t)fd.v[2] * C;
+        for (int k = 0; k < C; ++k) out[k] = (lam[0] * c0[k] + lam[1] * c1[k]) + lam[2] * c2[k];
+    }
+    if (!M::RESOLVE)
+        covbits[o] = (AB & 32) ? (uint8_t)0
+                               : (uint8_t)neighbour_coverage(rp, E, fd.clipped != 0, best_rec, frame_recs, fdata_frame, F,
+                                                             face_of_record(best_rec, F), i, j, resolve_small);
+    PHASE_TS(5);
+}
+
 // NOPIX (Gouraud): coverage-only resolve for dirt_rasterise_bwd_recompute -- the g-buffer and the
 // neighbour-coverage bits the backward reads, no pixels (no background or colour loads, no pixel stores).
 template <int CC, int AB = 0, int SH = DIRT_SHADER_GOURAUD, bool GB = false, bool FUSED = false, bool NOPIX = false,
@@ -526,7 +753,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                                                      const uint32_t *__restrict__ stash_hdr, const DeepArgs dga,
                                                      const int32_t *__restrict__ gb_in)
 {
-    constexpr bool kNoDepth = SH == DIRT_SHADER_HILL;
+    using M = RasterMode<CC, AB, SH, GB, FUSED, NOPIX, OCC, RESOLVE>;
+    constexpr bool kNoDepth = M::kNoDepth;
     static_assert(!(GB && kNoDepth), "hill has no depth buffer");
     static_assert(!FUSED || SH == DIRT_SHADER_GOURAUD, "the fused small-scene forward is Gouraud only");
     static_assert(!NOPIX || (SH == DIRT_SHADER_GOURAUD && !GB), "the coverage-only resolve is Gouraud only");
@@ -538,7 +766,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     __shared__ Rec s_recs[FUSED ? (1 + kExtraPerFace) * kFusedMaxF : 1];
     __shared__ FaceData s_fd[FUSED ? kFusedMaxF : 1];
     PHASE_TS(0);
-    constexpr int CM = CC > 0 ? CC : DIRT_MAX_CHANNELS;
     const int C = CC > 0 ? CC : Cdyn;
     __shared__ int32_t t_list[kStrips][kFilterBlock];  // per-wave segments of the tile's survivors
     __shared__ int32_t t_nw[2][kStrips];                // segment lengths, double-buffered by chunk parity
@@ -571,29 +798,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     const float fxl = (float)pi + 0.5f, fyl = (float)pj + 0.5f;
     const Rec *frame_recs = FUSED ? s_recs : recs + (int64_t)b * nrec;
     const FaceData *fdata_frame = FUSED ? s_fd : fdata + (int64_t)b * F;
-    if constexpr (FUSED) {
-        if (t < F) {
-            bool oob;
-            // (only the workgroup of tile 0 counts the R5 deviations: every workgroup repeats the frame's setup)
-            s_fd[t] = setup_face_into(verts + (int64_t)b * V * 4, faces + ((int64_t)b * F + t) * 3, V, F, W, H, t,
-                                      s_recs, oob, blockIdx.x == 0 ? flag : nullptr);
-            if (oob) atomicOr(flag, 1u);
-        }
-        __syncthreads();
-        if (blockIdx.x == 0) {
-            // publish the frame's records and FaceData for the backward (plain stores; the backward is a
-            // later launch)
-            Rec *gr = const_cast<Rec *>(recs) + (int64_t)b * nrec;
-            for (int k = t; k < (int)nrec; k += 256) {
-                const int f = face_of_record(k, F);
-                const int s = k < F ? 0 : (k - F) - (f * kExtraPerFace) + 1;
-                if (k < F || s < s_fd[f].nsub) gr[k] = s_recs[k];
-            }
-            if (t < F) const_cast<FaceData *>(fdata)[(int64_t)b * F + t] = s_fd[t];
-        }
-    }
+    if constexpr (FUSED) fused_frame_setup(s_recs, s_fd, b, verts, faces, V, F, W, H, flag, recs, fdata, nrec);
 
-
+    // ---- first loads, then the launch's housekeeping behind them
     uint64_t best = kKeyInit<kNoDepth>;
     const short2v pix = {(short)dx, (short)dy};  // lane offset from the tile origin in sub-pixels
     const float2v pxy = {fxl, fyl};
@@ -630,37 +837,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     // of the frame is filtered (the overflow path)
     const uint32_t raw = RESOLVE ? 0u : FUSED ? 0xffffffffu
                                : F > 0 ? counts[cc * kCountStride] + counts[((int64_t)B * ncoarse + cc) * kCountStride] : 0u;
-    if (!FUSED && !RESOLVE && blockIdx.x == 0 && blockIdx.y == 0 && t == 0 && !(AB & 16)) flag[kParQ] = (flag[kParP] & 1u) ^ 1u;
-    if (dga.host != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
-        // automatic deep culling: report whether the previous launch on this scratch was deep (to the host-mapped
-        // word the host reads when it picks the next launch's instantiation), then clear its count slot
-        uint32_t *prev = &flag[kDeepCnt + 4 * (dga.slot ^ 1u)];
-        const uint32_t sampled = gridDim.y * ((gridDim.x + kDeepSample - 1) / kDeepSample);
-        if (dga.prev_gen != 0u && *prev >= max(1u, sampled / kDeepFrac))
-            __hip_atomic_store(dga.host, dga.prev_gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        *prev = 0u;
-    }
-    if (!(AB & 16)) {
-        // housekeeping spread over all blocks (a few KB each): zero-fill the caller's gradient
-        // accumulators if it passed them (after the slab loads are in flight)
-        const int64_t nblk = (int64_t)gridDim.x * gridDim.y;
-        const int64_t gt = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x, gs = nblk * 256;
-        // (16-B stores where the caller's buffer is 16-B aligned -- torch allocations are -- else scalar)
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (zero_a) {
-            const int64_t n4 = (reinterpret_cast<uintptr_t>(zero_a) & 15) == 0 ? (nzero_a >> 2) : 0;
-            for (int64_t k = gt; k < n4; k += gs) reinterpret_cast<float4 *>(zero_a)[k] = z4;
-            for (int64_t k = 4 * n4 + gt; k < nzero_a; k += gs) zero_a[k] = 0.f;
-        }
-        if (zero_b) {
-            const int64_t n4 = (reinterpret_cast<uintptr_t>(zero_b) & 15) == 0 ? (nzero_b >> 2) : 0;
-            for (int64_t k = gt; k < n4; k += gs) reinterpret_cast<float4 *>(zero_b)[k] = z4;
-            for (int64_t k = 4 * n4 + gt; k < nzero_b; k += gs) zero_b[k] = 0.f;
-        }
-    }
+    launch_housekeeping<M>(flag, dga, zero_a, nzero_a, zero_b, nzero_b);
     // the recompute backward's coverage pass: nothing more to do on a stash hit (the workspace already holds this
     // geometry's g-buffer and coverage bits; the Q parity above republished the value it had, setup having skipped)
     if (NOPIX && stash_hdr != nullptr && stash_hit(stash_hdr)) return;
+
+    // ---- visibility pass: filter, stage and walk; leaves the lane's best key in `best`
     // an overflowed slab (more pairs than its capacity): filter every record of the frame instead
     const bool overflow = FUSED || raw > slab;
     const uint32_t n_items = overflow ? (uint32_t)nrec : raw;
@@ -729,46 +911,21 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
                 __syncthreads();
             }
             for (int from = 0; from < ((AB & 2) ? 0 : n_list); from += 256) {
-                const int g = from + t;
-                uint32_t m = 0;
-                if (g < n_list) {
-                    int w = 0;
-#pragma unroll
-                    for (int q = 1; q < kStrips; ++q) w += g >= pre[q] ? 1 : 0;
-                    const int32_t ri = t_list[w][g - pre[w]];
-                    StripEntry E;
-                    bool large;
-                    m = stage_tile(frame_recs, ri, ti0, tj0, F, E, large);
-                    int4 *d = reinterpret_cast<int4 *>(&t_ent[t]);
-                    d[0] = make_int4(E.e[0], E.e[1], E.e[2], (int)E.ab[0]);
-                    d[1] = make_int4((int)E.ab[1], (int)E.ab[2], __float_as_int(E.za), __float_as_int(E.zb));
-                    d[2] = make_int4(__float_as_int(E.fx0), __float_as_int(E.fy0), (int)E.key, __float_as_int(E.z0));
-                    m |= large ? 16u : 0u;
-                }
-                t_mask[t] = (uint8_t)m;
+                stage_round(from + t, n_list, pre, t_list, frame_recs, ti0, tj0, F, &t_ent[t], &t_mask[t]);
                 __syncthreads();
                 if (chunk == 0 && from == 0) PHASE_TS(2);
                 const int nst = min(256, n_list - from);
                 if (!(AB & 1)) {
-                    // this wave's entries as a list (ballot compaction of the round's masks): the loop then
-                    // walks offsets read two at a time instead of scanning a bit mask on the scalar unit
-                    int ns = 0, nl = 0;
-                    for (int c0 = 0; c0 < nst; c0 += 64) {
-                        const uint32_t mm = c0 + lane < nst ? t_mask[c0 + lane] : 0u;
-                        const bool mine = (mm >> wave) & 1u, big = (mm >> 4) & 1u;
-                        const uint64_t bs = __ballot(mine && !big), bl = __ballot(mine && big);
-                        if (mine && !big) t_wl[wave][ns + lane_rank(bs)] = (uint32_t)(c0 + lane) * sizeof(StripEntry);
-                        if (mine && big) t_wl[wave][kWaveList - 1 - (nl + lane_rank(bl))] = (uint32_t)(c0 + lane);
-                        ns += __popcll(bs);
-                        nl += __popcll(bl);
-                    }
-                    if (lane == 0) t_wl[wave][ns] = 256u * sizeof(StripEntry);  // pad / sentinel
+                    const WaveList wlen = build_wave_list(t_mask, t_wl[wave], nst, wave, lane);
+                    int ns = wlen.ns;
+                    const int nl = wlen.nl;
                     // automatic deep culling: one workgroup in kDeepSample counts the long lists of its wave 0 (one
                     // non-returning atomic per such staging round: the counter is a single word)
                     if (dga.host != nullptr && wave == 0 && lane == 0 && (blockIdx.x & (kDeepSample - 1)) == 0 &&
                         ns > kDeepMark)
                         atomicAdd(&flag[kDeepCnt + 4 * dga.slot], 1u);
                     wave_lds_sync();
+                    // -- the list walk (inline: see the note above the phases)
                     // two entries per iteration; the next pair's offsets are read before this pair is
                     // tested (reads at k + 2 <= ns + 1 stay inside the list)
                     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -833,6 +990,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
         }
     }
     PHASE_TS(3);
+
+    // ---- resolve: the visible record, then the pixel's outputs
 #if DIRT_RASTER_REMAT_IJ
     // the lane's pixel again, from an opaque copy of threadIdx.x: the compiler cannot reuse the values computed
     // before the chunk loop, so they need not stay live (in VGPRs) across it
@@ -855,32 +1014,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
         gbuffer[o] = (int32_t)best;
         return;
     }
-    int32_t best_rec;
-    if constexpr (RESOLVE) {
-        const int32_t g = gb_in[o];
-        best_rec = g >= 0 ? (g & kGbufIndexMask) : -1;
-    } else {
-        best_rec = best != kKeyInit<kNoDepth> ? key_rec(key_low<kNoDepth>(best), F) : -1;
-    }
+    const int32_t best_rec = resolve_record<M>(best, gb_in, o, F);
     if (best_rec < 0) {
-        gbuffer[o] = -1;
-        if constexpr (GB) {
-            if (gbo.depth) gbo.depth[o] = 1.0f;
-            if (gbo.bary) {
-                gbo.bary[o * 3] = 0.0f;
-                gbo.bary[o * 3 + 1] = 0.0f;
-                gbo.bary[o * 3 + 2] = 0.0f;
-            }
-            if (gbo.face) gbo.face[o] = -1;
-        }
-        if constexpr (SH == DIRT_SHADER_GOURAUD && !RESOLVE) covbits[o] = 0;
-        if constexpr (!NOPIX) {
-#pragma unroll
-            for (int c2 = 0; c2 < CM; ++c2)
-                if (c2 < C) out[c2] = kNoDepth ? 0.0f : background[o * C + c2];  // (hill: no background copy)
-        }
-        PHASE_TS(4);
-        PHASE_TS(5);
+        write_uncovered<M>(o, C, background + o * C, out, gbuffer, covbits, gbo);
         return;
     }
     int32_t best_q = best_rec;
@@ -898,6 +1034,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
     const RasterPart rp = *reinterpret_cast<const RasterPart *>(&r);
     const FaceData fd = fdata_frame[face_of_record(best_rec, F)];
     gbuffer[o] = best_rec | (fd.clipped ? kGbufMulti : 0);
+    // -- the record's edge values E at the pixel and the barycentrics lam of its face's three vertices (R6; inline:
+    // see the note above the phases)
     int64_t E[3];
     float lam[3] = {0.0f, 0.0f, 0.0f};
     float fE[3];
@@ -939,90 +1077,42 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_
 #pragma unroll
     for (int k = 0; k < 3; ++k) iwv[k] = fd.clipped ? r.iw[k] : fd.q[k];
     parent_lambda_f(r, iwv, fE, fd.clipped == 0, lam);
-    if constexpr (GB) {
-        if (gbo.depth) gbo.depth[o] = (float)(uint32_t)(best >> 32) / 16777215.0f;
-        if (gbo.bary) {
-            gbo.bary[o * 3] = lam[0];
-            gbo.bary[o * 3 + 1] = lam[1];
-            gbo.bary[o * 3 + 2] = lam[2];
-        }
-        if (gbo.face) gbo.face[o] = face_of_record(best_rec, F);
-    }
+    if constexpr (GB) write_gbuf_outputs(gbo, o, best, lam, face_of_record(best_rec, F));
     PHASE_TS(4);
+    // -- shade: a procedural program from texCoordV (the oceanic ones jittered), or Gouraud
     if constexpr (SH == DIRT_SHADER_OCEANIC_HORIZON) {
-        // texCoordV = perspective-correct clip xy (shaders.cpp:19,21 alias texCoord to position); jitter by
-        // the background texel at (texCoordV+1)/2 (NEAREST), channels x,y (C=1 broadcast)
-        const float *vb = verts + (int64_t)b * V * 4;
-        const float *p0 = vb + (int64_t)fd.v[0] * 4, *p1 = vb + (int64_t)fd.v[1] * 4, *p2 = vb + (int64_t)fd.v[2] * 4;
-        const float tx = (lam[0] * p0[0] + lam[1] * p1[0]) + lam[2] * p2[0];
-        const float ty = (lam[0] * p0[1] + lam[1] * p1[1]) + lam[2] * p2[1];
-        const float u = (tx + 1.0f) / 2.0f, v = (ty + 1.0f) / 2.0f;
-        int ix = (int)floorf(u * (float)W), iy = (int)floorf(v * (float)H);
-        if (!(u * (float)W >= 0.0f)) ix = 0;
-        if (!(v * (float)H >= 0.0f)) iy = 0;
-        ix = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix);
-        iy = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy);
-        const float *texel = background + (((int64_t)b * H + (H - 1 - iy)) * W + ix) * C;
-        const float sx = texel[0], sy = C >= 2 ? texel[1] : texel[0];
+        const float2 tc = tex_coord_v(verts + (int64_t)b * V * 4, fd, lam);
+        const float tx = tc.x, ty = tc.y;
+        const float2 jt = jitter_texel(background, b, H, W, C, (tx + 1.0f) / 2.0f, (ty + 1.0f) / 2.0f);
+        const float sx = jt.x, sy = jt.y;
         const ocean::Camera camv{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
         const float2 col = ocean::shade(tx + sx / (float)W, ty + sy / (float)H, camv, (float)W, (float)H);
         for (int k = 0; k < C; ++k) out[k] = k == 0 ? col.x : k == 1 ? col.y : k == 3 ? 1.0f : 0.0f;
     } else if constexpr (SH == DIRT_SHADER_HILL) {
         // hill: texCoordV without jitter; the op's background tensor is the terrain lookup (tcb channels)
-        const float *vb = verts + (int64_t)b * V * 4;
-        const float *p0 = vb + (int64_t)fd.v[0] * 4, *p1 = vb + (int64_t)fd.v[1] * 4, *p2 = vb + (int64_t)fd.v[2] * 4;
-        const float tx = (lam[0] * p0[0] + lam[1] * p1[0]) + lam[2] * p2[0];
-        const float ty = (lam[0] * p0[1] + lam[1] * p1[1]) + lam[2] * p2[1];
+        const float2 tc = tex_coord_v(verts + (int64_t)b * V * 4, fd, lam);
+        const float tx = tc.x, ty = tc.y;
         const hill::Tex T{background + (int64_t)b * H * W * tcb, H, W, tcb};
         const float4 col = hill::shade(T, tx, ty, cam);
         for (int k = 0; k < C; ++k) out[k] = k == 0 ? col.x : k == 1 ? col.y : k == 2 ? col.z : k == 3 ? col.w : 0.0f;
     } else if constexpr (SH == DIRT_SHADER_OCEANIC) {
         // the oceanic family (shader ids 2..6, `sid` at run time), same texCoordV and jitter as above
-        const float *vb = verts + (int64_t)b * V * 4;
-        const float *p0 = vb + (int64_t)fd.v[0] * 4, *p1 = vb + (int64_t)fd.v[1] * 4, *p2 = vb + (int64_t)fd.v[2] * 4;
-        const float tx = (lam[0] * p0[0] + lam[1] * p1[0]) + lam[2] * p2[0];
-        const float ty = (lam[0] * p0[1] + lam[1] * p1[1]) + lam[2] * p2[1];
+        const float2 tc = tex_coord_v(verts + (int64_t)b * V * 4, fd, lam);
+        const float tx = tc.x, ty = tc.y;
         if (sid == DIRT_SHADER_OCEANIC_OPT_FLOW) {
             // no jitter (shaders.cpp:1323-1325 commented out); fragColor = (new_coord, 0, 1)
             const float2 nc = ocean::opt_flow(tx, ty, cam, (float)W, (float)H);
             for (int k = 0; k < C; ++k) out[k] = k == 0 ? nc.x : k == 1 ? nc.y : k == 3 ? 1.0f : 0.0f;
             return;
         }
-        const float u = (tx + 1.0f) / 2.0f, v = (ty + 1.0f) / 2.0f;
-        int ix = (int)floorf(u * (float)W), iy = (int)floorf(v * (float)H);
-        if (!(u * (float)W >= 0.0f)) ix = 0;
-        if (!(v * (float)H >= 0.0f)) iy = 0;
-        ix = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix);
-        iy = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy);
-        const float *texel = background + (((int64_t)b * H + (H - 1 - iy)) * W + ix) * C;
-        const float sx = texel[0], sy = C >= 2 ? texel[1] : texel[0];
+        const float2 jt = jitter_texel(background, b, H, W, C, (tx + 1.0f) / 2.0f, (ty + 1.0f) / 2.0f);
+        const float sx = jt.x, sy = jt.y;
         const float3 col = ocean::shade_family(ocean::family_params(sid), tx + sx / (float)W, ty + sy / (float)H, cam,
                                                (float)W, (float)H);
         for (int k = 0; k < C; ++k) out[k] = k == 0 ? col.x : k == 1 ? col.y : k == 2 ? col.z : k == 3 ? 1.0f : 0.0f;
     } else {
-        if constexpr (NOPIX) {
-            // (coverage only: the caller holds the pixels)
-        } else if (AB & 64) {
-            for (int k = 0; k < C; ++k) out[k] = lam[k % 3];
-        } else {
-            const float *cb = colors + (int64_t)b * V * C;
-            if (AB & 1024) {
-                // ablation: one extra dependent global round trip between the FaceData and the colour loads
-                uint32_t z0, z1;
-                asm volatile("v_mov_b32 %0, 0" : "=v"(z0) : "v"(fd.v[0]));
-                const uint32_t w = flag[kParQ + z0];
-                asm volatile("v_mov_b32 %0, 0" : "=v"(z1) : "v"(w));
-                cb += z1;
-            }
-            const float *c0 = cb + (int64_t)fd.v[0] * C, *c1 = cb + (int64_t)fd.v[1] * C, *c2 = cb + (int64_t)fd.v[2] * C;
-            for (int k = 0; k < C; ++k) out[k] = (lam[0] * c0[k] + lam[1] * c1[k]) + lam[2] * c2[k];
-        }
-        if (!RESOLVE)
-        covbits[o] = (AB & 32) ? (uint8_t)0
-                               : (uint8_t)neighbour_coverage(rp, E, fd.clipped != 0, best_rec, frame_recs,
-                                                             fdata_frame, F, face_of_record(best_rec, F), i, j,
-                                                             resolve_small);
-        PHASE_TS(5);
+        shade_gouraud<M>(b, frame_recs, fdata_frame, colors, V, C, F, fd, rp, E, lam, resolve_small, best_rec, i, j, o, out,
+                         covbits, flag);
     }
 }
 
@@ -1063,13 +1153,17 @@ inline RasterLaunch raster_launch(const Layout &L, int B, int H, int W, int C, i
     return a;
 }
 
-// The one place that launches raster_kernel, and so the one place that knows its parameter order.
-template <int CC, int AB = 0, int SH = DIRT_SHADER_GOURAUD, bool GB = false, bool FUSED = false, bool NOPIX = false,
-          bool OCC = false, bool RESOLVE = false>
+// The kernel's mode switches by name (launch_raster's MODE: any combination the kernel's static_asserts admit)
+constexpr unsigned kRasterGbuf = 1, kRasterFused = 2, kRasterNoPix = 4, kRasterOcc = 8, kRasterResolve = 16;
+
+// The one place that launches raster_kernel, and so the one place that knows its parameter order, the template's
+// included: MODE expands to the kernel's five bools.
+template <int CC, unsigned MODE = 0, int SH = DIRT_SHADER_GOURAUD, int AB = 0>
 void launch_raster(const RasterLaunch &a)
 {
     const dim3 grid((unsigned)a.ntiles, (unsigned)a.B);
-    raster_kernel<CC, AB, SH, GB, FUSED, NOPIX, OCC, RESOLVE><<<grid, dim3(256), 0, a.stream>>>(
+    raster_kernel<CC, AB, SH, (MODE & kRasterGbuf) != 0, (MODE & kRasterFused) != 0, (MODE & kRasterNoPix) != 0,
+                  (MODE & kRasterOcc) != 0, (MODE & kRasterResolve) != 0><<<grid, dim3(256), 0, a.stream>>>(
         a.background, a.colors, a.recs, a.fdata, a.counts, a.flag, a.bins, a.slab, a.B, a.H, a.W, a.C, a.V, a.F,
         tile_grid(a.ntx), a.cshift, a.nctx, a.ncoarse, a.nrec, a.pixels, a.gbuffer, a.covbits, a.zero_a,
         a.zero_a ? (int64_t)a.B * a.V * 4 : 0, a.zero_b, a.zero_b ? (int64_t)a.B * a.V * a.C : 0, a.verts, a.cam, a.sid,

@@ -270,8 +270,17 @@ __device__ __forceinline__ uint32_t rel_bbox(uint32_t bx, uint32_t by, int cx, i
     return (uint32_t)a0 | ((uint32_t)a1 << 8) | ((uint32_t)b0 << 16) | ((uint32_t)b1 << 24);
 }
 
-// Zero-fill of two float arrays by a range of workgroups (16-B stores where the buffer is 16-B aligned --
-// torch allocations are -- else scalar)
+// Zero the n floats at p, as thread gt of gs threads that share the work: 16-B stores where the buffer is 16-B
+// aligned -- torch allocations are -- then the tail (everything, where it is not) with scalar stores
+__device__ __forceinline__ void zero_strided(float *p, int64_t n, int64_t gt, int64_t gs)
+{
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t n4 = (reinterpret_cast<uintptr_t>(p) & 15) == 0 ? (n >> 2) : 0;
+    for (int64_t k = gt; k < n4; k += gs) reinterpret_cast<float4 *>(p)[k] = z4;
+    for (int64_t k = 4 * n4 + gt; k < n; k += gs) p[k] = 0.f;
+}
+
+// Zero-fill of two float arrays (either may be null) by a range of workgroups
 struct ZeroFill {
     float *a, *b;
     int64_t na, nb;
@@ -279,17 +288,8 @@ struct ZeroFill {
     __device__ void run(int64_t blk, int64_t nblk) const
     {
         const int64_t gt = blk * blockDim.x + threadIdx.x, gs = nblk * blockDim.x;
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a) {
-            const int64_t n4 = (reinterpret_cast<uintptr_t>(a) & 15) == 0 ? (na >> 2) : 0;
-            for (int64_t k = gt; k < n4; k += gs) reinterpret_cast<float4 *>(a)[k] = z4;
-            for (int64_t k = 4 * n4 + gt; k < na; k += gs) a[k] = 0.f;
-        }
-        if (b) {
-            const int64_t n4 = (reinterpret_cast<uintptr_t>(b) & 15) == 0 ? (nb >> 2) : 0;
-            for (int64_t k = gt; k < n4; k += gs) reinterpret_cast<float4 *>(b)[k] = z4;
-            for (int64_t k = 4 * n4 + gt; k < nb; k += gs) b[k] = 0.f;
-        }
+        if (a) zero_strided(a, na, gt, gs);
+        if (b) zero_strided(b, nb, gt, gs);
     }
 };
 

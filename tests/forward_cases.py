@@ -45,6 +45,9 @@ for _s in range(5):
 for _C in (1, 3, 7, 5):
     CASES["channels_%d" % _C] = functools.partial(scenes.random_triangles, F=60, W=40, H=24, C=_C, radius_px=10.0,
                                                   seed=30 + _C, perspective=True)
+    # at most kFusedMaxF = 32 faces: the fused small-scene forward (no setup launch, no bins) of the channel class
+    CASES["channels_fused_%d" % _C] = functools.partial(scenes.random_triangles, F=32, W=40, H=24, C=_C,
+                                                        radius_px=10.0, seed=40 + _C, perspective=True)
 for _W, _H in SIZES:
     _t = "_%dx%d" % (_W, _H)
     CASES["clipped" + _t] = functools.partial(_clipped, _W, _H)

@@ -9,11 +9,12 @@ Each forward path at the smallest shape at which it exists: the fused small-scen
 binned one on the same two 40x24 frames (F = 33; partial tiles right and bottom); the binned path with slabs
 too small for its bins (the overflow fallback); the occluder-culling raster forced on the deep stacks; clipped
 faces, interpenetrating pairs, near / far straddlers, exact ties and the flat-depth known answers at 33x17 and
-64x48; the channel classes 1, 3, 7 and 5 (generic); 1x17 and 17x1 frames.
+64x48; the channel classes 1, 3, 7 and 5 (generic), binned (F = 60) and fused (F = 32); 1x17 and 17x1 frames.
 
 Measured on an MI355X, worst |kernel - exact| / (2^-24 sum |terms|) over these cases: depth 1.73 (k = 8,
 clipped_64x48), barycentrics 4.79 (k = 13) and colours 4.80 (k = 16) on near_far_outside_64x48 -- the CPU table's
-figures, as the kernels are bit-identical to the oracle; undecided at most 1.66 % (deep stacks).  26 tests in 5 s.
+figures, as the kernels are bit-identical to the oracle; undecided at most 1.66 % (deep stacks).  30 tests, each
+under a second.
 """
 import numpy as np
 import pytest
@@ -119,10 +120,13 @@ def test_flat_depth_known_answers(size):
             assert (depth[rows, x0:x1] == np.float32(d) / np.float32(M)).all(), q
 
 
-@pytest.mark.parametrize("C", [1, 3, 7, 5])
-def test_channel_classes(C):
-    """The channel specialisations 1, 3, 7 and the generic one (5), 60 overlapping perspective faces at 40x24."""
-    run_and_check("channels_%d" % C)
+@pytest.mark.parametrize("name", ["channels_%d" % C for C in (1, 3, 7, 5)] +
+                         ["channels_fused_%d" % C for C in (1, 3, 7, 5)],
+                         ids=["1", "3", "7", "5", "fused_1", "fused_3", "fused_7", "fused_5"])
+def test_channel_classes(name):
+    """The channel specialisations 1, 3, 7 and the generic one (5) at 40x24: 60 overlapping perspective faces
+    (setup + binned raster), and 32 (the fused small-scene raster), each plain and with the G-buffer outputs."""
+    run_and_check(name)
 
 
 @pytest.mark.parametrize("name", ["line_1x17", "line_17x1"])
