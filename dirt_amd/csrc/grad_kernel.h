@@ -595,9 +595,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GradGeom<TWX, TH>::NT),
             // branches.  A neighbour shows my face iff it shows my record (a non-clipped face has exactly
             // one).  Ownership code: outside the frame 0, background 2, same face 2 for the
             // lower pixel of the pair / 0 for the upper, else 1 + (q's face covers p) - (p's face covers q).
-            // The pair weight of vertex k is c_d * m_k with m_k = (2 E_k +- 256 A_k (or B_k)) / w_k =
-            // P_k +- Q_k and c_d = code_d * s_d * (W/2 or H/2) / (4D), so the two pairs of an axis fold
-            // into (c_0 + c_1) P_k + (c_0 - c_1) Q_k (and the same with the NDC factors for w).
+            // The pair weight of vertex k is c_d * m_kd with m_kd = (2 E_k +- 256 A_k (or B_k)) / w_k and
+            // c_d = code_d * s_d * (W/2 or H/2) / (4D) (and the same with the NDC factors for w).
             // packed layout: the own pixel's two halves once, each neighbour's two halves (G, I, its g-buffer word and
             // coverage bits) as two ds_read_b128
             float4 Gme, Ime;
@@ -642,18 +641,20 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GradGeom<TWX, TH>::NT),
             }
             const float ndc_r = (float)(i + 1) * inv_hw - 1.0f, ndc_l = (float)i * inv_hw - 1.0f;
             const float ndc_u = (float)(j + 1) * inv_hh - 1.0f, ndc_d = (float)j * inv_hh - 1.0f;
-            const float ux = cd[0] + cd[1], vx = cd[0] - cd[1];
-            const float uwx = cd[0] * ndc_r + cd[1] * ndc_l, vwx = cd[0] * ndc_r - cd[1] * ndc_l;
-            const float uy = cd[2] + cd[3], vy = cd[2] - cd[3];
-            const float uwy = cd[2] * ndc_u + cd[3] * ndc_d, vwy = cd[2] * ndc_u - cd[3] * ndc_d;
+            // Each pair's midpoint value 2 E_k +- step is formed before it is scaled (one rounding, relative to
+            // the midpoint value itself: both operands are exact below 2^24).  Folding the two pairs of an axis
+            // into (c_0 + c_1) P_k + (c_0 - c_1) Q_k rounded P_k and Q_k apart, and a midpoint within a pixel of
+            // the edge opposite vertex k (P_k ~ -Q_k) lost up to 130 times the term's own rounding
+            // (tests/test_gpu_backward_bound.py).
+            const float cwr = cd[0] * ndc_r, cwl = cd[1] * ndc_l, cwu = cd[2] * ndc_u, cwd = cd[3] * ndc_d;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const float iwk = k == 0 ? iw0 : k == 1 ? iw1 : iw2;
-                const float P = (2.0f * fEp[k]) * iwk;
-                const float Qx = ((float)mA[k] * 256.0f) * iwk, Qy = ((float)mB[k] * 256.0f) * iwk;
-                acc[k * 3 + 0] += ux * P + vx * Qx;
-                acc[k * 3 + 1] += uy * P + vy * Qy;
-                acc[k * 3 + 2] -= (uwx * P + vwx * Qx) + (uwy * P + vwy * Qy);
+                const float e2 = 2.0f * fEp[k], sa = (float)mA[k] * 256.0f, sb = (float)mB[k] * 256.0f;
+                const float mr = (e2 + sa) * iwk, ml = (e2 - sa) * iwk, mu = (e2 + sb) * iwk, md = (e2 - sb) * iwk;
+                acc[k * 3 + 0] += cd[0] * mr + cd[1] * ml;
+                acc[k * 3 + 1] += cd[2] * mu + cd[3] * md;
+                acc[k * 3 + 2] -= (cwr * mr + cwl * ml) + (cwu * mu + cwd * md);
             }
             PHASE_TS(11 + (acc[0] == 12345.f));
         } else {

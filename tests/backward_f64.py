@@ -25,6 +25,9 @@ pinned separately -- coverage by tests/exact_cover.py, depth, clipping, the visi
 values by tests/forward_exact.py (exact plane depth with derived float32 bounds; the oracle against it in
 tests/test_forward_exact.py, the HIP kernels in tests/test_gpu_forward_exact.py).  Pure-Python loops: small
 frames only.
+
+backward_with_bounds / backward_batch_with_bounds return the same values and, per element, the sum of the absolute
+values of its terms and their number (Bounds): what the per-element contract of tests/backward_cases.py is stated in.
 """
 import numpy as np
 
@@ -117,6 +120,15 @@ class Tri:
         Wm = sum(mu[k] * self.w[k] for k in range(3))
         return lam, Wm
 
+    def abs_weights(self, E2):
+        """The absolute parts of `weights` at the same point: sum_k |b_k / w_k| |basis_ki| (of lambda_i / Wm =
+        sum_k (b_k / w_k) basis_ki, the b_k summing to 1) and sum_k |mu_k| |basis_ki| (of lambda_i)."""
+        q = [abs(e / (2.0 * self.D)) / self.w[k] for k, e in enumerate(E2)]
+        sq = sum(e / (2.0 * self.D) / self.w[k] for k, e in enumerate(E2))
+        pair = [sum(q[k] * abs(self.basis[k][i]) for k in range(3)) for i in range(3)]
+        col = [sum(q[k] / abs(sq) * abs(self.basis[k][i]) for k in range(3)) for i in range(3)]
+        return pair, col
+
 
 CAP_CULLS = [0]  # faces culled by R5's vertex cap so far (tests)
 
@@ -175,10 +187,10 @@ def _record(tris, F, ri):
     return f, tris[f][0][d - f * EXTRA_PER_FACE + 1]
 
 
-def backward(vertices, faces, pixels, grad_pixels, gbuffer):
+def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None):
     """One frame: vertices [V,4], faces [F,3], pixels / grad_pixels [H,W,C] (rows top first), gbuffer [H,W]
     (visible record, bit 30 = clipped face, -1 background).  Returns float64 (grad_vertices [V,4],
-    grad_vertex_colors [V,C], grad_background [H,W,C])."""
+    grad_vertex_colors [V,C], grad_background [H,W,C]).  track: a Bounds to fill next to them (backward_with_bounds)."""
     H, W, C = pixels.shape
     V, F = vertices.shape[0], faces.shape[0]
     tris = [setup_face(vertices, faces[f], V, W, H) for f in range(F)]
@@ -205,8 +217,11 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer):
             lam, _ = t.weights([2 * e for e in t.E(256 * i + 128, 256 * j + 128)])
             for k in range(3):
                 gc[faces[f][k]] += lam[k] * G[at(i, j)]
+            if track is not None:
+                track.colour(faces[f], t, [2 * e for e in t.E(256 * i + 128, 256 * j + 128)], lam, G[at(i, j)],
+                             tris[f][1], (i, j))
 
-    def add(ri, i, j, axis, s, omega):
+    def add(ri, i, j, axis, s, omega, s_abs=0.0):
         f, t = _record(tris, F, int(ri))
         if axis == 0:
             E2 = [t.A[k] * (512 * i + 512) + t.B[k] * (512 * j + 256) + 2 * t.C[k] for k in range(3)]
@@ -219,6 +234,9 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer):
             g = omega * s * half * lam[k] / Wm
             gv[faces[f][k], axis] += g
             gv[faces[f][k], 3] -= g * ndc
+        if track is not None:
+            track.pair(faces[f], t, E2, axis, omega, s, s_abs, half, ndc, [lam[k] / Wm for k in range(3)], tris[f][1],
+                       (i, j), int(ri))
 
     for j in range(H):
         for i in range(W):
@@ -235,27 +253,103 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer):
                 s = -0.5 * float(np.sum((G[at(i, j)] + G[at(i2, j2)]) * (Iq - Ip)))
                 if s == 0.0:
                     continue
+                sa = 0.0 if track is None else 0.5 * float(np.sum(
+                    (np.abs(G[at(i, j)]) + np.abs(G[at(i2, j2)])) * np.abs(Iq - Ip)))
                 fp = _record(tris, F, rp)[0] if rp >= 0 else -1
                 fq = _record(tris, F, rq)[0] if rq >= 0 else -1
                 if fp == fq or fq < 0:
-                    add(rp, i, j, axis, s, 1.0)
+                    add(rp, i, j, axis, s, 1.0, sa)
                 elif fp < 0:
-                    add(rq, i, j, axis, s, 1.0)
+                    add(rq, i, j, axis, s, 1.0, sa)
                 else:
                     p_covers_q, q_covers_p = face_covers(fp, i2, j2), face_covers(fq, i, j)
                     if not p_covers_q and q_covers_p:
-                        add(rp, i, j, axis, s, 1.0)
+                        add(rp, i, j, axis, s, 1.0, sa)
                     elif p_covers_q and not q_covers_p:
-                        add(rq, i, j, axis, s, 1.0)
+                        add(rq, i, j, axis, s, 1.0, sa)
                     else:
-                        add(rp, i, j, axis, s, 0.5)
-                        add(rq, i, j, axis, s, 0.5)
+                        add(rp, i, j, axis, s, 0.5, sa)
+                        add(rq, i, j, axis, s, 0.5, sa)
     return gv, gc, gbg
 
 
 def backward_batch(vertices, faces, pixels, grad_pixels, gbuffer):
     outs = [backward(vertices[b], faces[b], pixels[b], grad_pixels[b], gbuffer[b]) for b in range(pixels.shape[0])]
     return tuple(np.stack([o[k] for o in outs]) for k in range(3))
+
+
+U32 = 2.0 ** -24  # float32's unit roundoff (round to nearest)
+
+
+class Bounds:
+    """What `backward` accumulates next to every gradient element for the per-element contract (DESIGN.md 5,
+    tests/test_gpu_backward_bound.py):
+      S_v [V,4], S_c [V,C]    the sum of the absolute values of the element's terms -- a term with every factor
+                              that can cancel replaced by its absolute parts:
+                                pair term into dL/dx_i, dL/dy_i   omega S_pair half sum_k |b_k / w_k| |basis_ki|,
+                                  S_pair = 0.5 sum_c (|G_c(p)| + |G_c(q)|) |I_c(q) - I_c(p)|,
+                                pair term into dL/dw_i            the same times |x_ndc(M)| (|y_ndc(M)|),
+                                colour term                       sum_k |mu_k| |basis_ki| |G_c(p)|;
+      n_v, n_c                the number of its non-zero terms;
+      clip_v [V,4], clip_c [V,C]   whether a clipped (sub-)record contributes to it;
+      N_v [V,4]               (column 3 only) sum over the element's terms of omega S_pair half sum_k |b_k / w_k|
+                              |basis_ki|: the dL/dx and dL/dy terms whose product with the float32 x_ndc the w
+                              component is -- x_ndc = mid (2 / W) - 1 carries an absolute rounding error, not one
+                              relative to |x_ndc|;
+      terms                   (keep_terms) every term as a dict, for tests that rebuild wrong sums from them.
+    Pairs the specification skips (a non-finite background on either side, s == 0) add nothing."""
+
+    def __init__(self, V, C, keep_terms=False):
+        self.S_v, self.n_v = np.zeros((V, 4)), np.zeros((V, 4), np.int64)
+        self.S_c, self.n_c = np.zeros((V, C)), np.zeros((V, C), np.int64)
+        self.N_v = np.zeros((V, 4))
+        self.clip_v, self.clip_c = np.zeros((V, 4), bool), np.zeros((V, C), bool)
+        self.terms = [] if keep_terms else None
+        self.n_half = 0  # pair owners with weight 0.5
+
+    def pair(self, f3, t, E2, axis, omega, s, s_abs, half, ndc, lam_w, clipped, pixel, ri):
+        aw, _ = t.abs_weights(E2)
+        self.n_half += omega == 0.5
+        for k in range(3):
+            v = int(f3[k])
+            g, ga = omega * s * half * lam_w[k], omega * s_abs * half * aw[k]
+            for col, val, va in ((axis, g, ga), (3, -g * ndc, ga * abs(ndc))):
+                self.S_v[v, col] += va
+                self.n_v[v, col] += val != 0.0
+                self.clip_v[v, col] |= bool(clipped) and val != 0.0
+            self.N_v[v, 3] += ga
+            if self.terms is not None:
+                self.terms.append(dict(kind="pair", vertex=v, axis=axis, pixel=pixel, record=ri, omega=omega, g=g,
+                                       ndc=ndc, abs=ga))
+
+    def colour(self, f3, t, E2, lam, G, clipped, pixel):
+        _, ac = t.abs_weights(E2)
+        for k in range(3):
+            v = int(f3[k])
+            val = lam[k] * G
+            self.S_c[v] += ac[k] * np.abs(G)
+            self.n_c[v] += val != 0.0
+            self.clip_c[v] |= bool(clipped) & (val != 0.0)
+            if self.terms is not None:
+                self.terms.append(dict(kind="colour", vertex=v, pixel=pixel, g=val))
+
+
+def backward_with_bounds(vertices, faces, pixels, grad_pixels, gbuffer, keep_terms=False):
+    """`backward` (the same values, bit for bit) and the Bounds of its elements."""
+    track = Bounds(vertices.shape[0], pixels.shape[2], keep_terms)
+    return backward(vertices, faces, pixels, grad_pixels, gbuffer, track) + (track,)
+
+
+def backward_batch_with_bounds(vertices, faces, pixels, grad_pixels, gbuffer, keep_terms=False):
+    """`backward_batch` and one Bounds per frame."""
+    outs = [backward_with_bounds(vertices[b], faces[b], pixels[b], grad_pixels[b], gbuffer[b], keep_terms)
+            for b in range(pixels.shape[0])]
+    return tuple(np.stack([o[k] for o in outs]) for k in range(3)) + ([o[3] for o in outs],)
+
+
+def stack_bounds(bounds, name):
+    """[B, ...] array of one field of a list of Bounds."""
+    return np.stack([getattr(b, name) for b in bounds])
 
 
 def max_rel_err(approx, exact):

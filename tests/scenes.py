@@ -514,3 +514,82 @@ def flat_depth_scene(W=64, H=48, C=3, seed=0):
     cols = rng.uniform(0, 1, size=(len(v), C)).astype(np.float32)
     bg = rng.uniform(0, 1, size=(H, W, C)).astype(np.float32)
     return (bg, v, cols, np.array(faces, np.int32)), spans
+
+
+def _window_scene(tris_px, W, H, C, seed, z=None, shared=None):
+    """Scene from triangles given in window pixels ([F,3,2], w = 1): split vertices (or `shared` = (points [V,2],
+    faces [F,3])), one random depth per face / vertex, random colours and background."""
+    rng = np.random.default_rng(seed)
+    if shared is None:
+        pts = np.asarray(tris_px, np.float64).reshape(-1, 2)
+        faces = np.arange(len(pts), dtype=np.int32).reshape(-1, 3)
+        zz = np.repeat(rng.uniform(-0.5, 0.5, len(faces)) if z is None else np.asarray(z, np.float64), 3)
+    else:
+        pts, faces = np.asarray(shared[0], np.float64), np.asarray(shared[1], np.int32)
+        zz = rng.uniform(-0.1, 0.1, len(pts)) if z is None else np.broadcast_to(z, (len(pts),))
+    ndc = pts * 2.0 / np.array([W, H], np.float64) - 1.0
+    v = np.concatenate([ndc, zz[:, None], np.ones((len(pts), 1))], 1).astype(np.float32)
+    cols = rng.uniform(0, 1, size=(len(v), C)).astype(np.float32)
+    bg = rng.uniform(0, 1, size=(H, W, C)).astype(np.float32)
+    return bg, v, cols, faces
+
+
+def pixel_triangles_scene(W=32, H=16, C=3, seed=0):
+    """One small triangle per pixel, covering that pixel's centre and no other: every pixel shows its own record
+    (the backward's slot table holds 64 per tile)."""
+    tris = [[[i + 0.1, j + 0.1], [i + 1.0, j + 0.1], [i + 0.1, j + 1.0]] for j in range(H) for i in range(W)]
+    return _window_scene(tris, W, H, C, seed)
+
+
+def stripe_scene(W=33, H=17, C=3, seed=0):
+    """One tall thin triangle per pixel column, covering every pixel centre of its column and none of its
+    neighbours': few records per tile, and every pixel a run of its own along its row."""
+    tris = [[[i + 0.05, -1.0], [i + 0.95, -1.0], [i + 0.5, 40.0 * H]] for i in range(W)]
+    return _window_scene(tris, W, H, C, seed)
+
+
+def tile_border_mesh_scene(W=48, H=32, C=3, seed=0, x0=16, x1=48, y0=8, y1=24, step=8):
+    """A shared-vertex grid mesh whose vertices lie on multiples of `step` pixels: its silhouette runs along x = x0 and
+    y = y0 and its internal shared edges along every multiple of `step` between (x = 32; y = 16 at the defaults),
+    the borders of the backward's tiles."""
+    xs, ys = np.arange(x0, x1 + 1, step), np.arange(y0, y1 + 1, step)
+    pts = [[x, y] for y in ys for x in xs]
+    n = len(xs)
+    faces = []
+    for r in range(len(ys) - 1):
+        for c in range(n - 1):
+            a = r * n + c
+            faces += [[a, a + 1, a + n], [a + 1, a + n + 1, a + n]]
+    return _window_scene(None, W, H, C, seed, shared=(pts, faces))
+
+
+def fan_scene(W=48, H=32, C=3, seed=0, n=64, radius=15.0):
+    """A closed fan of n faces around one shared vertex at the frame's centre (valence n)."""
+    ang = np.linspace(0.0, 2.0 * np.pi, n, endpoint=False)
+    cx, cy = W / 2.0 + 0.3, H / 2.0 + 0.2
+    pts = [[cx, cy]] + [[cx + radius * np.cos(a), cy + radius * np.sin(a)] for a in ang]
+    faces = [[0, 1 + k, 1 + (k + 1) % n] for k in range(n)]
+    return _window_scene(None, W, H, C, seed, shared=(pts, faces))
+
+
+def large_record_scene(W=64, H=48, C=3, seed=0, far=False):
+    """Small triangles (r = 5 px) in front of three large ones: edges of 100 to 200 px, or with far = True vertices
+    thousands of pixels outside the frame (inside the guard band, so not clipped)."""
+    rng = np.random.default_rng(seed)
+    bg, v, c, f = random_triangles(F=40, W=W, H=H, C=C, radius_px=5.0, seed=seed)
+    v = v.copy()
+    v[:, 2] = v[:, 2] * 0.4 - 0.5
+    s = 80.0 if far else 1.0  # (the guard band reaches 16384 px from the frame's centre)
+    big = np.array([[[-60 * s, -40 * s], [130 * s, 10], [20, 110 * s]],
+                    [[-90, 60], [150, -30 * s], [70, 140]],
+                    [[10, -70 * s], [170 * s, 40], [-60 * s, 90]]], np.float64)
+    _, vb, cb, fb = _window_scene(big, W, H, C, seed + 1, z=rng.uniform(0.2, 0.8, 3))
+    return bg, np.concatenate([v, vb]), np.concatenate([c, cb]), np.concatenate([f, fb + len(v)]).astype(np.int32)
+
+
+def pixel_centre_edge_scene(W=33, H=17, C=3, seed=0):
+    """Two rectangles (two faces each) whose edges pass exactly through pixel centres (x = 4.5, 12.5, 20.5;
+    y = 3.5, 11.5), abutting along x = 12.5: R3's top-left rule decides those pixels."""
+    pts = [[4.5, 3.5], [12.5, 3.5], [20.5, 3.5], [4.5, 11.5], [12.5, 11.5], [20.5, 11.5]]
+    faces = [[0, 1, 4], [0, 4, 3], [1, 2, 5], [1, 5, 4]]
+    return _window_scene(None, W, H, C, seed, shared=(pts, faces))

@@ -51,7 +51,9 @@ def run_gpu(bg, v, c, f, grad_pixels=None, bin_capacity=0):
 
 def assert_close_grad(gpu, ref, name, strict=False):
     """gpu vs ref within RTOL |ref| + ATOL_REL scale (strict: the STRICT pair of the tensor named by `name`'s
-    first word)."""
+    first word).  This scale-relative contract remains for large frames only, where the float64 statement is too
+    slow: one sliver's gradient sets the tolerance of every other vertex, and small elements go all but unchecked.
+    tests/test_gpu_backward_bound.py holds the kernel to the float64 statement element by element instead."""
     rtol, atol_rel = STRICT[name.split()[0]] if strict else (RTOL, ATOL_REL)
     finite_ref = np.abs(ref[np.isfinite(ref)])
     scale = max(float(finite_ref.max()) if finite_ref.size else 0.0, 1e-30)
