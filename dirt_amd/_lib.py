@@ -34,6 +34,7 @@ FWD_DEEP_CULL = 2      # dirt_rasterise_fwd: occluder culling for deep scenes (f
 FWD_DEEP_CULL_OFF = 8  # dirt_rasterise_fwd: never the occluder culling
 TEXTURE_CLAMP = 0      # dirt_texture_sample_* wrap modes
 TEXTURE_REPEAT = 1
+MAX_MIP_LEVELS = 14    # dirt_texture_mip_*: the chain of an 8192 x 8192 texture
 BWD_ACCUMULATE = 1    # dirt_rasterise_bwd / dirt_rasterise_bwd_recompute flags
 BWD_SCRATCH_CLEAN = 2  # dirt_rasterise_bwd_recompute: the workspace's bin counters are clean
 
@@ -77,6 +78,13 @@ SIGNATURES = {
                                      _P, _P]),
     "dirt_texture_sample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dirt_texture_sample_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dirt_texture_mip_layout": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_longlong),
+                                     ctypes.POINTER(ctypes.c_longlong)]),
+    "dirt_texture_mip_build_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "dirt_texture_mip_build_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "dirt_texture_sample_mip_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _I, _I, _I, _I, _P, _P,
+                                         _P, _P]),
+    "dirt_texture_sample_mip_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dirt_last_error": (ctypes.c_char_p, []),
 }
 

@@ -291,6 +291,7 @@ struct EventPair {
 #include "lighting_kernels.h"
 #include "deferred_kernels.h"
 #include "texture_kernels.h"
+#include "texture_mip_kernels.h"
 
 // zero two float arrays in one launch (the backward's atomically accumulated outputs)
 __global__ __launch_bounds__(256) void zero2_kernel(float *__restrict__ a, int64_t na, float *__restrict__ b, int64_t nb)
@@ -1607,6 +1608,200 @@ int dirt_texture_sample_bwd(const float *texture, int texture_frames, int Th, in
     with_each_channel_count(C, [&](auto c) {
         launch_texture_bwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, B, H, W, wrap, grad_texels, grad_texture,
                                                grad_uv, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- mipmapped deferred texturing: the chain build, the trilinear lookup and their gradients (texture_mip_kernels.h)
+
+namespace {
+
+// number of levels of the chain of a Th x Tw texture, truncated to max_levels when that is positive
+int mip_chain_length(int Th, int Tw, int max_levels)
+{
+    int L = 1, h = Th, w = Tw;
+    while (L < kMaxMipLevels && (max_levels <= 0 || L < max_levels) && !(h == 1 && w == 1) &&
+           (h == 1 || h % 2 == 0) && (w == 1 || w % 2 == 0)) {
+        h = h > 1 ? h / 2 : 1;
+        w = w > 1 ? w / 2 : 1;
+        ++L;
+    }
+    return L;
+}
+
+// the texture-side argument checks of the mip entry points: DIRT_OK with *L the number of levels (levels <= 0: the
+// whole chain) and *texels the texels of one frame of the packed chain
+int mip_sizes(const char *op, int texture_frames, int Th, int Tw, int C, int levels, int *L, int64_t *texels)
+{
+    char msg[160];
+    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM) {
+        snprintf(msg, sizeof(msg), "%s: texture height, width must be in 1..%d", op, DIRT_MAX_DIM);
+        return fail(DIRT_EINVAL, msg);
+    }
+    if (C < 1 || C > DIRT_MAX_CHANNELS) {
+        snprintf(msg, sizeof(msg), "%s: expects 1 <= channels <= %d", op, DIRT_MAX_CHANNELS);
+        return fail(DIRT_EINVAL, msg);
+    }
+    if (texture_frames < 0) {
+        snprintf(msg, sizeof(msg), "%s: texture_frames must be non-negative", op);
+        return fail(DIRT_EINVAL, msg);
+    }
+    const int full = mip_chain_length(Th, Tw, 0);
+    if (levels > full) {
+        snprintf(msg, sizeof(msg), "%s: levels = %d, but the chain of a %d x %d texture has %d", op, levels, Th, Tw,
+                 full);
+        return fail(DIRT_EINVAL, msg);
+    }
+    *L = levels <= 0 ? full : levels;
+    *texels = mip_level(Th, Tw, *L).off;
+    if (((int64_t)texture_frames * Th * Tw * C + kLightThreads - 1) / kLightThreads > 0x7fffffffLL) {
+        snprintf(msg, sizeof(msg), "%s: too large (more texture elements than one launch covers)", op);
+        return fail(DIRT_EINVAL, msg);
+    }
+    return DIRT_OK;
+}
+
+int mip_sample_sizes(int texture_frames, int Th, int Tw, int C, int levels, int B, int H, int W, int wrap, int *L,
+                     int64_t *texels, int64_t *pixels)
+{
+    int rc = deferred_sizes("texture_sample_mip", B, H, W, C, pixels);
+    if (rc) return rc;
+    const int64_t n = *pixels;
+    *pixels = 0;
+    rc = mip_sizes("texture_sample_mip", texture_frames, Th, Tw, C, levels, L, texels);
+    if (rc) return rc;
+    if (wrap != DIRT_TEXTURE_CLAMP && wrap != DIRT_TEXTURE_REPEAT)
+        return fail(DIRT_EINVAL, "texture_sample_mip: wrap must be DIRT_TEXTURE_CLAMP or DIRT_TEXTURE_REPEAT");
+    if (B > 0 && texture_frames != 1 && texture_frames != B)
+        return fail(DIRT_EINVAL, "texture_sample_mip: texture_frames must be 1 or the batch size");
+    const int64_t tiles = (int64_t)((H + kTexTile - 1) / kTexTile) * ((W + kTexTile - 1) / kTexTile);
+    if ((int64_t)B * tiles > 0x7fffffffLL)
+        return fail(DIRT_EINVAL, "texture_sample_mip: too large (more screen tiles than one launch covers)");
+    *pixels = n;
+    return DIRT_OK;
+}
+
+template <int C>
+void launch_texture_mip_fwd(const float *packed, int64_t frame_stride, int Th, int Tw, int L, const float *uv,
+                            const uint8_t *mask, const float *lod_in, float lod_bias, int H, int W, int64_t n, int wrap,
+                            float *texels, uint8_t *valid, float *lod, hipStream_t stream)
+{
+    texture_sample_mip_fwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        packed, frame_stride, Th, Tw, L, uv, mask, lod_in, lod_bias, H, W, n, wrap, texels, valid, lod);
+}
+
+template <int C>
+void launch_texture_mip_bwd(const float *packed, int64_t frame_stride, int Th, int Tw, int L, const float *uv,
+                            const uint8_t *mask, const float *lod, int B, int H, int W, int wrap, const float *grad,
+                            float *grad_packed, float *grad_uv, hipStream_t stream)
+{
+    const int tiles_x = (W + kTexTile - 1) / kTexTile, tiles_y = (H + kTexTile - 1) / kTexTile;
+    texture_sample_mip_bwd_kernel<C>
+        <<<dim3((unsigned)((int64_t)B * tiles_y * tiles_x)), dim3(kLightThreads), 0, stream>>>(
+            packed, frame_stride, Th, Tw, L, uv, mask, lod, H, W, tiles_x, tiles_y, wrap, grad, grad_packed, grad_uv);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_texture_mip_layout(int Th, int Tw, int max_levels, int *dims, long long *offsets, long long *total)
+{
+    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM) {
+        (void)fail(DIRT_EINVAL, "texture_mip_layout: texture height, width must be in 1..8192");
+        return 0;
+    }
+    const int L = mip_chain_length(Th, Tw, max_levels);
+    MipLevel lv = mip_level(Th, Tw, 0);
+    for (int k = 0; k < L; ++k, lv = mip_next(lv)) {
+        if (dims) {
+            dims[2 * k] = lv.h;
+            dims[2 * k + 1] = lv.w;
+        }
+        if (offsets) offsets[k] = lv.off;
+    }
+    if (total) *total = lv.off;
+    return L;
+}
+
+int dirt_texture_mip_build_fwd(const float *texture, int texture_frames, int Th, int Tw, int C, int levels,
+                               float *packed, void *stream_)
+{
+    int L;
+    int64_t N;
+    const int rc = mip_sizes("texture_mip_build", texture_frames, Th, Tw, C, levels, &L, &N);
+    if (rc || texture_frames == 0) return rc;
+    if (!texture || !packed) return fail(DIRT_EINVAL, "texture_mip_build: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = N * C, n0 = (int64_t)Th * Tw * C;
+    mip_copy_kernel<<<dim3(light_blocks(texture_frames * n0)), dim3(kLightThreads), 0, stream>>>(
+        texture, n0, fs, texture_frames * n0, packed);
+    MipLevel src = mip_level(Th, Tw, 0);
+    for (int k = 1; k < L; ++k) {
+        const MipLevel dst = mip_next(src);
+        const int64_t n = (int64_t)texture_frames * dst.h * dst.w * C;
+        mip_down_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+            packed, fs, src.off * C, src.h, src.w, dst.off * C, dst.h, dst.w, C, n);
+        src = dst;
+    }
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_texture_mip_build_bwd(const float *grad_packed, int texture_frames, int Th, int Tw, int C, int levels,
+                               float *grad_texture, void *stream_)
+{
+    int L;
+    int64_t N;
+    const int rc = mip_sizes("texture_mip_build", texture_frames, Th, Tw, C, levels, &L, &N);
+    if (rc || texture_frames == 0) return rc;
+    if (!grad_packed || !grad_texture) return fail(DIRT_EINVAL, "texture_mip_build: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t n = (int64_t)texture_frames * Th * Tw * C;
+    mip_build_bwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(grad_packed, N * C, Th, Tw, C, L, n,
+                                                                                    grad_texture);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_texture_sample_mip_fwd(const float *packed, int texture_frames, int Th, int Tw, int C, int levels,
+                                const float *uv, const uint8_t *mask, const float *lod_in, float lod_bias, int B, int H,
+                                int W, int wrap, float *texels, uint8_t *valid, float *lod, void *stream_)
+{
+    int L;
+    int64_t N, n;
+    const int rc = mip_sample_sizes(texture_frames, Th, Tw, C, levels, B, H, W, wrap, &L, &N, &n);
+    if (rc || n == 0) return rc;
+    if (!(lod_bias - lod_bias == 0.0f)) return fail(DIRT_EINVAL, "texture_sample_mip: lod_bias must be finite");
+    if (!packed || !uv || !texels || !valid || !lod) return fail(DIRT_EINVAL, "texture_sample_mip: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = texture_frames == 1 ? 0 : N * C;
+    with_each_channel_count(C, [&](auto c) {
+        launch_texture_mip_fwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod_in, lod_bias, H, W, n, wrap,
+                                                   texels, valid, lod, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_texture_sample_mip_bwd(const float *packed, int texture_frames, int Th, int Tw, int C, int levels,
+                                const float *uv, const uint8_t *mask, const float *lod, int B, int H, int W, int wrap,
+                                const float *grad_texels, float *grad_packed, float *grad_uv, void *stream_)
+{
+    int L;
+    int64_t N, n;
+    const int rc = mip_sample_sizes(texture_frames, Th, Tw, C, levels, B, H, W, wrap, &L, &N, &n);
+    if (rc || n == 0 || (!grad_packed && !grad_uv)) return rc;
+    if (!packed || !uv || !lod || !grad_texels) return fail(DIRT_EINVAL, "texture_sample_mip: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = texture_frames == 1 ? 0 : N * C;
+    if (grad_packed) HIP_TRY(hipMemsetAsync(grad_packed, 0, (size_t)texture_frames * N * C * sizeof(float), stream));
+    with_each_channel_count(C, [&](auto c) {
+        launch_texture_mip_bwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod, B, H, W, wrap, grad_texels,
+                                                   grad_packed, grad_uv, stream);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;

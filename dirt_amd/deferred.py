@@ -8,6 +8,9 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
   dilate(x, mask=None)     [H,W,C] or [B,H,W,C]: the 3x3 max where mask is set (default: any channel is +-inf)
   shade(positions, colors, normals, ...) -> (pixels, valid)
   sample_texture(texture, uv, mask=None, wrap="clamp") -> (texels, valid): bilinear texture lookup at a uv G-buffer
+  build_mipmaps(texture, levels=None) -> Mipmaps: the box-filtered mip chain, packed
+  sample_texture_mip(mipmaps_or_texture, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0) -> (texels, valid):
+                           trilinear lookup of the chain, the level chosen per pixel from the uv differences
 
 On the GPU both run as one fused HIP launch forward and one backward (dirt_amd/csrc/deferred_kernels.h, C ABI
 dirt_dilate_* / dirt_deferred_shade_*) when their operands are float32 tensors on one GPU and the light parameters
@@ -22,6 +25,10 @@ sample_texture is the step between the two: UV -> texel, with gradients to the t
 geometry (dirt_amd/csrc/texture_kernels.h, C ABI dirt_texture_sample_*; the statement is `_sample_texture_ops`).  Its
 uv gradient is a gather in a fixed order too; its texture gradient is a scatter-add summed with float atomics (per
 screen tile in an LDS patch first), so it may differ in the last bits from run to run, as vertex_normals' does.
+
+build_mipmaps and sample_texture_mip are its minification-safe form (dirt_amd/csrc/texture_mip_kernels.h, C ABI
+dirt_texture_mip_* / dirt_texture_sample_mip_*; the statements are `_build_mipmaps_ops`, `_sample_texture_mip_ops`),
+with the same eligibility and fallback.  The level of detail is a constant of the backward: it carries no gradient.
 """
 import os
 
@@ -312,3 +319,320 @@ def sample_texture(texture, uv, mask=None, wrap="clamp"):
         texels, valid = _SampleTextureFn.apply(tb, ub, mb, _WRAPS[wrap])
         return (texels, valid) if uv.dim() == 4 else (texels[0], valid[0])
     return _sample_texture_ops(texture, uv, mask, wrap)
+
+
+# ---- mipmapped texture sampling
+
+def _mip_dims(Th, Tw, levels=None):
+    """[(Th_k, Tw_k)] of the chain: level k + 1 exists while level k has every dimension even or 1 and not both 1."""
+    dims = [(int(Th), int(Tw))]
+    while levels is None or len(dims) < levels:
+        h, w = dims[-1]
+        if (h == 1 and w == 1) or (h > 1 and h % 2) or (w > 1 and w % 2):
+            break
+        dims.append((max(1, h // 2), max(1, w // 2)))
+    return dims
+
+
+class Mipmaps:
+    """A packed mip chain: `packed` [N,C] (shared by the frames) or [B,N,C] (one per frame), N = sum_k Th_k * Tw_k, the
+    levels in order, each row-major; `dims` = ((Th_0, Tw_0), ...); `level(k)` a [..., Th_k, Tw_k, C] view of packed;
+    len() the number of levels.  build_mipmaps makes the box-filtered chain; Mipmaps(packed, Th, Tw, levels) wraps a
+    chain filtered any other way (levels=None: the whole chain of a Th x Tw texture)."""
+
+    def __init__(self, packed, Th, Tw, levels=None):
+        packed = torch.as_tensor(packed)
+        if levels is not None and (int(levels) != levels or levels < 1):
+            raise ValueError("Mipmaps: levels must be a positive integer or None")
+        if Th < 1 or Tw < 1:
+            raise ValueError("Mipmaps: the texture must be non-empty")
+        dims = _mip_dims(Th, Tw, levels)
+        if levels is not None and len(dims) != levels:
+            raise ValueError("Mipmaps: levels = %d, but the chain of a %d x %d texture has %d"
+                             % (levels, Th, Tw, len(dims)))
+        n = sum(h * w for h, w in dims)
+        if packed.dim() not in (2, 3) or packed.shape[-2] != n or packed.shape[-1] < 1 or packed.shape[0] < 1:
+            raise ValueError("Mipmaps: packed must be [N, C] or [B, N, C] with N = %d for %d levels of a %d x %d "
+                             "texture, not %s" % (n, len(dims), Th, Tw, tuple(packed.shape)))
+        self.packed, self.dims = packed, tuple(dims)
+        self.offsets = tuple(sum(h * w for h, w in dims[:k]) for k in range(len(dims)))
+
+    def __len__(self):
+        return len(self.dims)
+
+    def level(self, k):
+        (h, w), o = self.dims[k], self.offsets[k]
+        return self.packed[..., o:o + h * w, :].unflatten(-2, (h, w))
+
+
+def _build_mipmaps_ops(texture, levels=None):
+    """texture [Th,Tw,C] or [B,Th,Tw,C] -> Mipmaps; each level the pairwise tree of the rule, one operation a line."""
+    dims = _mip_dims(texture.shape[-3], texture.shape[-2], levels)
+    chain = [texture]
+    for h, w in dims[:-1]:
+        t = chain[-1]
+        if h >= 2 and w >= 2:
+            top = t[..., 0::2, 0::2, :] + t[..., 0::2, 1::2, :]
+            bot = t[..., 1::2, 0::2, :] + t[..., 1::2, 1::2, :]
+            chain.append((top + bot) * 0.25)
+        elif w >= 2:
+            chain.append((t[..., :, 0::2, :] + t[..., :, 1::2, :]) * 0.5)
+        else:
+            chain.append((t[..., 0::2, :, :] + t[..., 1::2, :, :]) * 0.5)
+    packed = torch.cat([t.flatten(-3, -2) for t in chain], -2)
+    return Mipmaps(packed, dims[0][0], dims[0][1], len(dims))
+
+
+class _BuildMipmapsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, texture, levels):
+        Tf, Th, Tw, C = texture.shape
+        n = sum(h * w for h, w in _mip_dims(Th, Tw, levels))
+        packed = torch.empty((Tf, n, C), dtype=torch.float32, device=texture.device)
+        with torch.cuda.device(texture.device):
+            _lib.check(_lib.load().dirt_texture_mip_build_fwd(texture.data_ptr(), Tf, Th, Tw, C, levels,
+                                                              packed.data_ptr(), _stream(texture.device)))
+        ctx.shape, ctx.levels = texture.shape, levels
+        return packed
+
+    @staticmethod
+    def backward(ctx, grad_packed):
+        _no_double_backward("build_mipmaps")
+        Tf, Th, Tw, C = ctx.shape
+        grad_packed = grad_packed.contiguous()
+        grad_texture = torch.empty(ctx.shape, dtype=torch.float32, device=grad_packed.device)
+        with torch.cuda.device(grad_packed.device):
+            _lib.check(_lib.load().dirt_texture_mip_build_bwd(grad_packed.data_ptr(), Tf, Th, Tw, C, ctx.levels,
+                                                              grad_texture.data_ptr(), _stream(grad_packed.device)))
+        return grad_texture, None
+
+
+def _mip_fused_texture(shape):
+    """the kernels' limits on a texture [..., Th, Tw, C]"""
+    return 1 <= shape[-1] <= _lib.MAX_CHANNELS and max(shape[-3], shape[-2]) <= _lib.MAX_DIM
+
+
+def build_mipmaps(texture, levels=None):
+    """The box-filtered mip chain of texture ([Th,Tw,C] or [B,Th,Tw,C]) as a Mipmaps, differentiable to the texture.
+    Level k + 1 halves level k (each texel the mean of its 2 x 2 block, of its pair where one dimension is 1) while
+    every dimension of level k is even or 1 and not both are 1: an odd dimension > 1 ends the chain (5 x 7: one level,
+    6 x 10: two, 64 x 64: seven).  levels=n keeps at most the first n levels."""
+    texture = torch.as_tensor(texture)
+    if texture.dim() not in (3, 4) or min(texture.shape) < 1:
+        raise ValueError("build_mipmaps: texture must be a non-empty [Th, Tw, C] or [B, Th, Tw, C]")
+    if levels is not None and (not isinstance(levels, int) or levels < 1):
+        raise ValueError("build_mipmaps: levels must be a positive integer or None")
+    if _FUSED_ENABLED and _gpu_f32(texture) and _mip_fused_texture(texture.shape):
+        dims = _mip_dims(texture.shape[-3], texture.shape[-2], levels)
+        tb = texture.contiguous() if texture.dim() == 4 else texture.contiguous()[None]
+        packed = _BuildMipmapsFn.apply(tb, len(dims))
+        return Mipmaps(packed if texture.dim() == 4 else packed[0], dims[0][0], dims[0][1], len(dims))
+    return _build_mipmaps_ops(texture, levels)
+
+
+def _mip_difference(uv, valid, dim):
+    """The rule's difference of uv ([...,H,W,2]) along dim (-3: y, -2: x): to the next pixel where there is one and it
+    is sampled, else from the previous one where there is one and it is sampled, else 0."""
+    n = uv.shape[dim]
+    if n == 1:
+        return torch.zeros_like(uv)
+    step = uv.narrow(dim, 1, n - 1) - uv.narrow(dim, 0, n - 1)  # step[i] = uv[i + 1] - uv[i]
+    zero = torch.zeros_like(uv.narrow(dim, 0, 1))
+    no = torch.zeros_like(valid.narrow(dim + 1, 0, 1))
+    use_next = torch.cat([valid.narrow(dim + 1, 1, n - 1), no], dim + 1)[..., None]
+    use_prev = torch.cat([no, valid.narrow(dim + 1, 0, n - 1)], dim + 1)[..., None]
+    return torch.where(use_next, torch.cat([step, zero], dim),
+                       torch.where(use_prev, torch.cat([zero, step], dim), torch.zeros_like(uv)))
+
+
+def _mip_lod_ops(uv, valid, Th, Tw, L, lod=None, lod_bias=0.0):
+    """The final level of detail [...,H,W] of the rule (0 at unsampled pixels), detached: it carries no gradient."""
+    uv = uv.detach()
+    if lod is None:
+        q = []
+        for dim in (-2, -3):
+            d = _mip_difference(uv, valid, dim)
+            du = d[..., 0] * Tw
+            dv = d[..., 1] * Th
+            q.append(du * du + dv * dv)
+        rho2 = torch.fmax(q[0], q[1])  # (a NaN loses against a number)
+        m, e = torch.frexp(torch.where(torch.isfinite(rho2), rho2, 1.0))  # rho2 = m * 2^e, m in [0.5, 1)
+        lod = 0.5 * ((e - 1).to(uv.dtype) + (m * 2.0 - 1.0))
+        lod = torch.where(rho2 >= 1.0, lod, 0.0)
+        lod = torch.where(torch.isinf(rho2), float(L - 1), lod)
+    else:
+        lod = lod.detach().to(uv.dtype)
+        lod = torch.where(torch.isnan(lod), 0.0, lod)
+    lod = lod + lod_bias
+    lod = torch.clamp(lod, 0.0, float(L - 1))
+    return torch.where(valid, lod, 0.0)
+
+
+class _BilinearFn(torch.autograd.Function):
+    """The bilinear rule on four gathered taps ([...,C]) and the two weights ([...,1]), each line one operation.  Its
+    backward takes the weights' gradients in the kernels' difference form,
+        grad_a = sum_c g_c * ((t01 - t00) * (1 - b) + (t11 - t10) * b),   grad_b = sum_c g_c * (bot_c - top_c),
+    so that a float32 gradient rounds texel differences, as the statement's bound counts, where plain autograd rounds
+    differences of products.  The backward is itself framework ops on the saved inputs: it differentiates again, with
+    every second derivative (the mixed one in a and b, and those between the weights and the taps)."""
+
+    @staticmethod
+    def forward(ctx, t00, t01, t10, t11, a, b):
+        ctx.save_for_backward(t00, t01, t10, t11, a, b)
+        oma, omb = 1.0 - a, 1.0 - b
+        top = t00 * oma + t01 * a
+        bot = t10 * oma + t11 * a
+        return top * omb + bot * b
+
+    @staticmethod
+    def backward(ctx, g):
+        t00, t01, t10, t11, a, b = ctx.saved_tensors
+        oma, omb = 1.0 - a, 1.0 - b
+        g_top, g_bot = g * omb, g * b
+        du = (t01 - t00) * omb + (t11 - t10) * b
+        top = t00 * oma + t01 * a
+        bot = t10 * oma + t11 * a
+        grad_a = (g * du).sum(-1, keepdim=True)
+        grad_b = (g * (bot - top)).sum(-1, keepdim=True)
+        return g_top * oma, g_top * a, g_bot * oma, g_bot * a, grad_a, grad_b
+
+
+def _mip_level_ops(texture, uv, sampled, wrap):
+    """`_sample_texture_ops`' rule at one level, for the pixels in `sampled`; the value is the rule's bit for bit, the
+    uv gradient is in the kernels' difference form (`_BilinearFn`), and it differentiates again."""
+    Th, Tw = texture.shape[-3], texture.shape[-2]
+    uvs = torch.where(sampled[..., None], uv, 0.0)  # (no index is ever formed from an unsampled pixel's uv)
+    j0, j1, a = _texture_axis(uvs[..., 0], Tw, wrap)
+    i0, i1, b = _texture_axis(uvs[..., 1], Th, wrap)
+    if texture.dim() == 4:
+        f = torch.arange(texture.shape[0], device=texture.device)[:, None, None]
+        t00, t01, t10, t11 = texture[f, i0, j0], texture[f, i0, j1], texture[f, i1, j0], texture[f, i1, j1]
+    else:
+        t00, t01, t10, t11 = texture[i0, j0], texture[i0, j1], texture[i1, j0], texture[i1, j1]
+    out = _BilinearFn.apply(t00, t01, t10, t11, a[..., None], b[..., None])
+    return torch.where(sampled[..., None], out, 0.0)
+
+
+def _sample_texture_mip_ops(mipmaps, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0):
+    """mipmaps a Mipmaps, uv [H,W,2] or [B,H,W,2], mask and lod (uv's shape without the channels) or None
+    -> (texels, valid, the final lod)."""
+    (Th, Tw), L = mipmaps.dims[0], len(mipmaps)
+    valid = torch.isfinite(uv).all(-1) if mask is None else mask != 0
+    lod = _mip_lod_ops(uv, valid, Th, Tw, L, lod, lod_bias)
+    k0f = torch.floor(lod)
+    f = (lod - k0f)[..., None]
+    k0 = k0f.to(torch.int64)
+    k1 = torch.clamp(k0 + 1, max=L - 1)
+    blend = valid & (f[..., 0] != 0)
+    s0 = torch.zeros(uv.shape[:-1] + (mipmaps.packed.shape[-1],), dtype=uv.dtype, device=uv.device)
+    s1 = s0
+    for k in range(L):  # (a level is read only by the pixels that the rule sends there)
+        at0, at1 = valid & (k0 == k), blend & (k1 == k)
+        if not bool((at0 | at1).any()):
+            continue
+        s = _mip_level_ops(mipmaps.level(k), uv, at0 | at1, wrap)
+        s0 = torch.where(at0[..., None], s, s0)
+        s1 = torch.where(at1[..., None], s, s1)
+    out = torch.where(blend[..., None], s0 * (1.0 - f) + s1 * f, s0)
+    return torch.where(valid[..., None], out, 0.0), valid[..., None], lod
+
+
+class _SampleTextureMipFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, packed, uv, mask, lod_in, Th, Tw, levels, wrap, lod_bias):
+        Tf, _, C = packed.shape
+        B, H, W, _ = uv.shape
+        dev = uv.device
+        texels = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        lod = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_texture_sample_mip_fwd(
+                packed.data_ptr(), Tf, Th, Tw, C, levels, uv.data_ptr(), _ptr(mask), _ptr(lod_in), lod_bias, B, H, W,
+                wrap, texels.data_ptr(), valid.data_ptr(), lod.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(packed, uv, mask, lod)
+        ctx.args = (Th, Tw, levels, wrap)
+        valid = valid.view(torch.bool)  # (the kernel writes 0 / 1)
+        ctx.mark_non_differentiable(valid, lod)
+        ctx.set_materialize_grads(False)  # (as sample_texture: no zero-filled "gradient" of valid or the lod)
+        return texels, valid, lod
+
+    @staticmethod
+    def backward(ctx, grad_texels, _grad_valid, _grad_lod):
+        _no_double_backward("sample_texture_mip")
+        if grad_texels is None:
+            return (None,) * 9
+        packed, uv, mask, lod = ctx.saved_tensors
+        Th, Tw, levels, wrap = ctx.args
+        Tf, _, C = packed.shape
+        B, H, W, _ = uv.shape
+        dev = uv.device
+        grad_texels = grad_texels.contiguous()
+        # (NULL for the gradient nobody needs: the kernel then skips it; grad_packed is zero-filled by the call)
+        grad_packed = torch.empty_like(packed) if ctx.needs_input_grad[0] else None
+        grad_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_texture_sample_mip_bwd(
+                packed.data_ptr(), Tf, Th, Tw, C, levels, uv.data_ptr(), _ptr(mask), lod.data_ptr(), B, H, W, wrap,
+                grad_texels.data_ptr(), _ptr(grad_packed), _ptr(grad_uv), _stream(dev)))
+        return (grad_packed, grad_uv) + (None,) * 7
+
+
+def _sample_texture_mip(mipmaps, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0):
+    """sample_texture_mip with the pixels' final lod as a third result (the buffer the fused backward reads)."""
+    fn = "sample_texture_mip"
+    if not isinstance(mipmaps, Mipmaps):
+        mipmaps = build_mipmaps(mipmaps)
+    packed = mipmaps.packed
+    uv = torch.as_tensor(uv, dtype=packed.dtype, device=packed.device)
+    if wrap not in _WRAPS:
+        raise ValueError("%s: wrap must be 'clamp' or 'repeat', not %r" % (fn, wrap))
+    if uv.dim() not in (3, 4) or uv.shape[-1] != 2:
+        raise ValueError("%s: uv must be [H, W, 2] or [B, H, W, 2]" % fn)
+    if packed.dim() == 3 and (uv.dim() != 4 or packed.shape[0] != uv.shape[0]):
+        raise ValueError("%s: a per-frame chain of shape %s for uv of shape %s"
+                         % (fn, tuple(packed.shape), tuple(uv.shape)))
+    if mask is not None:
+        mask = torch.as_tensor(mask, device=uv.device)
+        if mask.shape != uv.shape[:-1]:
+            raise ValueError("%s: mask of shape %s for uv of shape %s" % (fn, tuple(mask.shape), tuple(uv.shape)))
+    if lod is not None:
+        lod = torch.as_tensor(lod, device=uv.device)
+        if lod.shape != uv.shape[:-1] or not lod.is_floating_point():
+            raise ValueError("%s: lod must be a float tensor of shape %s, not %s"
+                             % (fn, tuple(uv.shape[:-1]), tuple(lod.shape)))
+    if isinstance(lod_bias, torch.Tensor) or not float("-inf") < float(lod_bias) < float("inf"):
+        raise ValueError("%s: lod_bias must be a finite number" % fn)
+    lod_bias = float(lod_bias)
+    (Th, Tw), L = mipmaps.dims[0], len(mipmaps)
+    if (_FUSED_ENABLED and _gpu_f32(packed, uv) and _mip_fused_texture((Th, Tw, packed.shape[-1])) and
+            L <= _lib.MAX_MIP_LEVELS and 1 <= min(uv.shape[-3:-1]) and max(uv.shape[-3:-1]) <= _lib.MAX_DIM and
+            (mask is None or mask.device == uv.device)):
+        pb = packed.contiguous() if packed.dim() == 3 else packed.contiguous()[None]
+        ub = uv.contiguous() if uv.dim() == 4 else uv.contiguous()[None]
+        mb = lb = None
+        if mask is not None:
+            mb = (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8).reshape(ub.shape[:-1])
+        if lod is not None:
+            lb = lod.detach().to(torch.float32).contiguous().reshape(ub.shape[:-1])
+        texels, valid, lod_out = _SampleTextureMipFn.apply(pb, ub, mb, lb, Th, Tw, L, _WRAPS[wrap], lod_bias)
+        return (texels, valid, lod_out) if uv.dim() == 4 else (texels[0], valid[0], lod_out[0])
+    return _sample_texture_mip_ops(mipmaps, uv, mask, wrap, lod, lod_bias)
+
+
+def sample_texture_mip(mipmaps, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0):
+    """Trilinear lookup of a mip chain (a Mipmaps, or a plain texture [Th,Tw,C] / [B,Th,Tw,C] whose chain is built
+    inside the call) at uv, with sample_texture's conventions for uv, mask, wrap and the two results (texels, valid).
+
+    Each sampled pixel takes its level of detail from the uv differences to its sampled neighbours (the next pixel in
+    x and in y where there is one, else the previous one, else 0), scaled to texels: rho2 = max(|d_x|^2, |d_y|^2),
+    lod = 0.5 * (e + m - 1) for rho2 = m * 2^e with m in [1, 2) -- log2 made piecewise linear, exact at powers of two;
+    0 for rho2 < 1.  lod ([H,W] or [B,H,W]) replaces that (a NaN in it counts as 0).  lod_bias is added, the sum
+    clamped to [0, levels - 1], and the result is sample_texture at level floor(lod) blended with the next level by
+    the fractional part (an integer lod reads one level only).
+
+    The lod carries no gradient: neither uv (through the differences) nor an explicit lod receives one from it.  The
+    uv gradient is the blend of the two levels' sample_texture gradients; the gradient to the chain, and through
+    build_mipmaps to the texture, reaches every texel under a minified pixel's footprint.  On the GPU the uv gradient
+    and build_mipmaps' backward are bit-identical from run to run; the chain's gradient is summed with float atomics."""
+    return _sample_texture_mip(mipmaps, uv, mask, wrap, lod, lod_bias)[:2]

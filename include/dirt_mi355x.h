@@ -78,7 +78,8 @@ extern "C" {
  * picks the occluder culling by itself (DIRT_FWD_DEEP_CULL forces it, + DIRT_FWD_DEEP_CULL_OFF); 13: +
  * dirt_rasterise_fwd_resolve; added at 13 without a bump, no signature or layout changed: dirt_dilate_fwd,
  * dirt_dilate_bwd, dirt_deferred_shade_fwd, dirt_deferred_shade_bwd, dirt_texture_sample_fwd,
- * dirt_texture_sample_bwd) */
+ * dirt_texture_sample_bwd, dirt_texture_mip_layout, dirt_texture_mip_build_fwd, dirt_texture_mip_build_bwd,
+ * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -350,6 +351,62 @@ int dirt_texture_sample_fwd(const float *texture, int texture_frames, int Th, in
 int dirt_texture_sample_bwd(const float *texture, int texture_frames, int Th, int Tw, int C, const float *uv,
                             const uint8_t *mask, int B, int H, int W, int wrap, const float *grad_texels,
                             float *grad_texture, float *grad_uv, void *stream);
+
+/* Mipmapped deferred texturing: a box-filtered mip chain of a texture and its trilinear lookup at a uv G-buffer.
+ * Chain of a texture [texture_frames,Th,Tw,C]: level 0 is the texture; level k+1 exists while level k has every
+ * dimension even or 1 and not both 1, with dimensions max(1, T/2) (an odd dimension > 1 ends the chain: 5x7 has 1
+ * level, 6x10 has 2, 64x64 has 7, 8192x8192 has 14 = DIRT_MAX_MIP_LEVELS).  float32, each sum and product rounded once:
+ *   both dimensions >= 2:  t'[i,j] = ((t[2i,2j] + t[2i,2j+1]) + (t[2i+1,2j] + t[2i+1,2j+1])) * 0.25
+ *   one dimension 1:       t'[j] = (t[2j] + t[2j+1]) * 0.5 along the other.
+ * packed [texture_frames,N,C], N = sum_k Th_k * Tw_k: the levels in order, each row-major.  `levels` truncates the
+ * chain (<= 0: the whole chain; more than the chain has: DIRT_EINVAL); the same value goes to all four entry points.
+ *
+ * dirt_texture_mip_layout is host-only (no GPU call): returns the number of levels L for max_levels (<= 0: the whole
+ * chain) and writes dims[2k], dims[2k+1] = Th_k, Tw_k, offsets[k] = the first texel of level k inside a frame, and
+ * *total = N (each pointer may be NULL; dims holds 2 * DIRT_MAX_MIP_LEVELS ints, offsets DIRT_MAX_MIP_LEVELS).  It
+ * returns 0, with a message in dirt_last_error, for dimensions outside 1..DIRT_MAX_DIM.
+ *
+ * dirt_texture_mip_build_fwd writes every level of packed (level 0 is a copy).  dirt_texture_mip_build_bwd takes
+ * grad_packed [texture_frames,N,C] (read only) to grad_texture [texture_frames,Th,Tw,C] (fully overwritten) as one
+ * gather per level-0 element in a fixed order, w_k = 0.25 or 0.5 the forward's box weight from level k to k+1:
+ *   acc = g[L-1][i >> (L-1), j >> (L-1)];  for k = L-2 .. 0:  acc = acc * w_k + g[k][i >> k, j >> k]
+ * (no atomics, no scratch buffer, bit-identical from run to run).  texture_frames == 0 is a no-op.
+ *
+ * Lookup.  uv [B,H,W,2], mask [B,H,W] uint8 (NULL = "both uv channels are finite"), conventions, limits and the
+ * per-level bilinear rule s_k as dirt_texture_sample_* with T = T_k.  Level of detail of a sampled pixel (y,x),
+ * float32, every step one IEEE operation, from the raw uv (before any wrap):
+ *   x-difference d = uv[y,x+1] - uv[y,x] if x+1 < W and that neighbour is sampled, else uv[y,x] - uv[y,x-1] if
+ *   x >= 1 and that neighbour is sampled, else 0; the y-difference alike;
+ *   du = d_u * Tw;  dv = d_v * Th;  q = du * du + dv * dv;  rho2 = fmax(qx, qy)  (a NaN loses against a number);
+ *   rho2 = m * 2^e, m in [1,2), both from the float's bit fields;  lod = 0.5 * (e + (m - 1));
+ *   lod = 0 unless rho2 >= 1 (0, subnormals, NaN);  lod = L-1 when rho2 is inf.
+ * lod_in [B,H,W] (nullable) replaces all of that; a NaN in it becomes 0.  Then lod = lod + lod_bias (finite), clamped
+ * to [0, L-1].  k0 = (int)floor(lod), f = lod - k0, k1 = min(k0+1, L-1):
+ *   out = s_k0 * (1 - f) + s_k1 * f;   f == 0: out = s_k0 and level k1 is not read.
+ * texels [B,H,W,C], valid [B,H,W] uint8 (0 / 1) and lod [B,H,W] (each pixel's final lod, 0 where unsampled) are fully
+ * overwritten; unsampled pixels give exactly 0 and valid 0, carry no gradient and form no address.
+ * THE LOD CARRIES NO GRADIENT, neither to uv nor to lod_in: the backward takes the forward's lod buffer as a constant.
+ * Backward, with g = grad_texels[p,:] at sampled pixels:
+ *   grad_packed[level k0, tap, c] += g_c * w1 * w2 * (1 - f), grad_packed[level k1, tap, c] += g_c * w1 * w2 * f for
+ *   the four taps of each level (w1, w2 the level's bilinear weights; f == 0: the four taps of k0 alone, weight 1);
+ *   grad_uv = grad_uv(k0) * (1 - f) + grad_uv(k1) * f, each term dirt_texture_sample_bwd's formula with T_k and its
+ *   pass rule (f == 0: grad_uv(k0)).
+ * grad_packed [texture_frames,N,C] is zero-filled on `stream` by the call (an asynchronous memset, capturable) and
+ * summed with float atomics (last bits may differ between calls); grad_uv [B,H,W,2] is a gather in a fixed order,
+ * bit-identical from run to run, zero at unsampled pixels.  Either may be NULL; with both NULL no launch is made.
+ * B == 0 is a no-op.  Every argument error is a return code raised before any GPU call. */
+#define DIRT_MAX_MIP_LEVELS 14
+int dirt_texture_mip_layout(int Th, int Tw, int max_levels, int *dims, long long *offsets, long long *total);
+int dirt_texture_mip_build_fwd(const float *texture, int texture_frames, int Th, int Tw, int C, int levels,
+                               float *packed, void *stream);
+int dirt_texture_mip_build_bwd(const float *grad_packed, int texture_frames, int Th, int Tw, int C, int levels,
+                               float *grad_texture, void *stream);
+int dirt_texture_sample_mip_fwd(const float *packed, int texture_frames, int Th, int Tw, int C, int levels,
+                                const float *uv, const uint8_t *mask, const float *lod_in, float lod_bias, int B, int H,
+                                int W, int wrap, float *texels, uint8_t *valid, float *lod, void *stream);
+int dirt_texture_sample_mip_bwd(const float *packed, int texture_frames, int Th, int Tw, int C, int levels,
+                                const float *uv, const uint8_t *mask, const float *lod, int B, int H, int W, int wrap,
+                                const float *grad_texels, float *grad_packed, float *grad_uv, void *stream);
 
 /* Thread-local message for the last non-OK return on this thread. */
 const char *dirt_last_error(void);

@@ -1,0 +1,468 @@
+"""Statement of record for mipmapped deferred texturing (dirt_amd.deferred.build_mipmaps / sample_texture_mip,
+dirt_amd/csrc/texture_mip_kernels.h), and its table of cases.  numpy only; it shares nothing with the implementations
+beyond texture_cases.sample, the per-level bilinear rule.  TEST INFRASTRUCTURE ONLY.
+
+Layout.  Level 0 is the texture [Th,Tw,C]; level k+1 exists while level k has every dimension even or 1 and not both
+1, with dimensions max(1, T/2); an odd dimension > 1 ends the chain.  `levels` truncates it.  Packed: [N,C] (or
+[Tf,N,C]), N = sum_k Th_k * Tw_k, the levels in order, each row-major.
+
+Chain, in the arithmetic `dtype` (float32: every line one IEEE operation):
+  both dimensions >= 2:  t'[i,j] = ((t[2i,2j] + t[2i,2j+1]) + (t[2i+1,2j] + t[2i+1,2j+1])) * 0.25
+  one dimension 1:       t'[j] = (t[2j] + t[2j+1]) * 0.5 along the other
+
+Level of detail of a sampled pixel (y,x), from the raw uv:
+  x-difference d = uv[y,x+1] - uv[y,x] if x+1 < W and that neighbour is sampled (branch 0), else uv[y,x] - uv[y,x-1]
+  if x >= 1 and that neighbour is sampled (branch 1), else 0 (branch 2); the y-difference alike
+  du = d_u * Tw;  dv = d_v * Th;  q = du * du + dv * dv;  rho2 = fmax(qx, qy)    (a NaN loses against a number)
+  rho2 = m * 2^e, m in [1,2) (frexp);  lod = 0.5 * (e + (m - 1));  0 unless rho2 >= 1;  L-1 when rho2 is inf
+An explicit lod replaces that (NaN -> 0).  Then lod = lod + lod_bias, clamped to [0, L-1].
+
+Trilinear: k0 = floor(lod), f = lod - k0, k1 = min(k0+1, L-1); s_k = texture_cases.sample at level k;
+out = s_k0 * (1 - f) + s_k1 * f, and out = s_k0 when f == 0 (level k1 is not read).  Unsampled pixels: exactly 0.
+
+sample_mip_vjp hands the forward's float32 coordinates and weights (a, b, 1-a, 1-b per level, f and 1-f) to float64
+products and sums (texture_cases.sample_vjp per level, the cotangent scaled by the level weight):
+  grad_packed[level, tap, c] += g_c * w1 * w2 * wl        wl = 1-f at k0 (1 when f == 0), f at k1 (absent when f == 0)
+  grad_uv = (1-f) * grad_uv(k0) + f * grad_uv(k1)
+with n, S per packed element and abs_uv per pixel as there.  The lod carries no gradient.
+
+chain_vjp is the build's backward, one gather per level-0 element, coarsest level first, in `dtype`:
+  acc = g[L-1][i >> (L-1), j >> (L-1)];  for k = L-2 .. 0:  acc = acc * w_k + g[k][i >> k, j >> k]
+w_k = 0.25 where level k has both dimensions >= 2, else 0.5.
+"""
+import functools
+
+import numpy as np
+
+import texture_cases as tc
+
+F32 = np.float32
+WRAPS = tc.WRAPS
+
+
+# ---- layout and chain
+
+def layout(Th, Tw, levels=None):
+    """-> (dims [(Th_k, Tw_k)], offsets [first texel of level k], N)"""
+    dims = [(int(Th), int(Tw))]
+    while levels is None or len(dims) < levels:
+        h, w = dims[-1]
+        if (h == 1 and w == 1) or (h > 1 and h % 2 == 1) or (w > 1 and w % 2 == 1):
+            break
+        dims.append((max(1, h // 2), max(1, w // 2)))
+    offsets = [0]
+    for h, w in dims:
+        offsets.append(offsets[-1] + h * w)
+    return dims, offsets[:-1], offsets[-1]
+
+
+def build_chain(texture, levels=None, dtype=F32):
+    """texture [Th,Tw,C] or [Tf,Th,Tw,C] -> the list of levels, each of texture's rank"""
+    dt = np.dtype(dtype).type
+    t = np.asarray(texture, dt)
+    dims, _, _ = layout(t.shape[-3], t.shape[-2], levels)
+    chain = [t]
+    for h, w in dims[:-1]:
+        t = chain[-1]
+        if h >= 2 and w >= 2:
+            top = t[..., 0::2, 0::2, :] + t[..., 0::2, 1::2, :]
+            bot = t[..., 1::2, 0::2, :] + t[..., 1::2, 1::2, :]
+            nxt = (top + bot) * dt(0.25)
+        elif w >= 2:
+            nxt = (t[..., :, 0::2, :] + t[..., :, 1::2, :]) * dt(0.5)
+        else:
+            nxt = (t[..., 0::2, :, :] + t[..., 1::2, :, :]) * dt(0.5)
+        assert nxt.dtype == dt
+        chain.append(nxt)
+    assert [c.shape[-3:-1] for c in chain] == dims
+    return chain
+
+
+def pack(chain):
+    """levels [..,h,w,C] -> [..,N,C]"""
+    return np.concatenate([c.reshape(c.shape[:-3] + (-1, c.shape[-1])) for c in chain], -2)
+
+
+def unpack(packed, Th, Tw, levels=None):
+    dims, offs, n = layout(Th, Tw, levels)
+    assert packed.shape[-2] == n
+    return [packed[..., o:o + h * w, :].reshape(packed.shape[:-2] + (h, w, packed.shape[-1]))
+            for (h, w), o in zip(dims, offs)]
+
+
+def chain_vjp(grad_packed, Th, Tw, levels=None, dtype=np.float64):
+    """grad_packed [..,N,C] -> grad_texture [..,Th,Tw,C], the gather of the module's docstring in `dtype`"""
+    dt = np.dtype(dtype).type
+    g = unpack(np.asarray(grad_packed, dt), Th, Tw, levels)
+    dims, _, _ = layout(Th, Tw, levels)
+    L = len(dims)
+    i, j = np.arange(Th)[:, None], np.arange(Tw)[None, :]
+    acc = g[L - 1][..., i >> (L - 1), j >> (L - 1), :]
+    for k in range(L - 2, -1, -1):
+        h, w = dims[k]
+        acc = acc * dt(0.25 if h >= 2 and w >= 2 else 0.5)
+        acc = acc + g[k][..., i >> k, j >> k, :]
+    assert acc.dtype == dt
+    return acc
+
+
+def chain_weights(Th, Tw, levels=None):
+    """W_k = w_0 * ... * w_(k-1): the weight of a level-k gradient element in the level-0 elements under it"""
+    dims, _, _ = layout(Th, Tw, levels)
+    W = [1.0]
+    for h, w in dims[:-1]:
+        W.append(W[-1] * (0.25 if h >= 2 and w >= 2 else 0.5))
+    return W
+
+
+# ---- level of detail
+
+def _difference(uv, valid, axis):
+    """-> (d [B,H,W,2], branch [B,H,W]: 0 next, 1 previous, 2 none) along axis 1 (y) or 2 (x)"""
+    n = uv.shape[axis]
+    d = np.zeros_like(uv)
+    branch = np.full(valid.shape, 2, np.int8)
+    if n == 1:
+        return d, branch
+    lo = [slice(None)] * 3
+    hi = [slice(None)] * 3
+    lo[axis], hi[axis] = slice(0, n - 1), slice(1, n)
+    lo, hi = tuple(lo), tuple(hi)
+    with np.errstate(invalid="ignore", over="ignore"):
+        step = uv[hi] - uv[lo]  # step[i] = uv[i+1] - uv[i]
+    use_next = np.zeros(valid.shape, bool)
+    use_next[lo] = valid[hi]
+    use_prev = np.zeros(valid.shape, bool)
+    use_prev[hi] = valid[lo]
+    use_prev &= ~use_next
+    d[lo] = np.where(use_next[lo][..., None], step, d[lo])
+    d[hi] = np.where(use_prev[hi][..., None], step, d[hi])
+    branch[use_next] = 0
+    branch[use_prev] = 1
+    return d, branch
+
+
+def lod_of(uv, valid, Th, Tw, L, lod=None, lod_bias=0.0, dtype=F32):
+    """-> dict: lod [B,H,W] (the final one, 0 at unsampled pixels), branch_x, branch_y (2 everywhere with an explicit
+    lod)"""
+    dt = np.dtype(dtype).type
+    uv = np.asarray(uv, dt)
+    bx = by = np.full(valid.shape, 2, np.int8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if lod is None:
+            q = []
+            for axis in (2, 1):
+                d, br = _difference(uv, valid, axis)
+                du = d[..., 0] * dt(Tw)
+                dv = d[..., 1] * dt(Th)
+                q.append(du * du + dv * dv)
+                if axis == 2:
+                    bx = br
+                else:
+                    by = br
+            rho2 = np.fmax(q[0], q[1])
+            assert rho2.dtype == dt
+            m, e = np.frexp(np.where(np.isfinite(rho2), rho2, dt(1)))  # m in [0.5, 1)
+            m = m * dt(2)
+            e = (e - 1).astype(dt)
+            lod = dt(0.5) * (e + (m - dt(1)))
+            lod = np.where(rho2 >= 1, lod, dt(0))
+            lod = np.where(np.isinf(rho2), dt(L - 1), lod)
+        else:
+            lod = np.asarray(lod, dt).reshape(valid.shape)
+            lod = np.where(np.isnan(lod), dt(0), lod)
+        lod = lod + dt(lod_bias)
+        lod = np.minimum(np.maximum(lod, dt(0)), dt(L - 1))
+    assert lod.dtype == dt
+    return {"lod": np.where(valid, lod, dt(0)), "branch_x": bx, "branch_y": by}
+
+
+# ---- lookup
+
+def sample_mip(chain, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0, dtype=F32):
+    """chain: the list of levels ([h,w,C] shared, or [Tf,h,w,C] with Tf == B); uv [B,H,W,2]; mask, lod [B,H,W] or None
+    -> dict: texels [B,H,W,C], valid, lod, k0, k1, f, omf, branch_x, branch_y [B,H,W], levels {k: the dict of
+    texture_cases.sample at level k, for the levels some pixel reads}"""
+    dt = np.dtype(dtype).type
+    uv = np.asarray(uv, dt)
+    B, H, W, _ = uv.shape
+    L = len(chain)
+    Th, Tw = chain[0].shape[-3:-1]
+    valid = np.isfinite(uv).all(-1) if mask is None else (np.asarray(mask).reshape(B, H, W) != 0)
+    out = lod_of(uv, valid, Th, Tw, L, lod, lod_bias, dtype)
+    k0f = np.floor(out["lod"])
+    f = out["lod"] - k0f
+    omf = dt(1) - f
+    k0 = k0f.astype(np.int64)
+    k1 = np.minimum(k0 + 1, L - 1)
+    blend = valid & (f != 0)
+    C = chain[0].shape[-1]
+    s0, s1, levels = np.zeros((B, H, W, C), dt), np.zeros((B, H, W, C), dt), {}
+    for k in range(L):
+        at0, at1 = valid & (k0 == k), blend & (k1 == k)
+        if not (at0 | at1).any():
+            continue
+        levels[k] = tc.sample(chain[k], uv, (at0 | at1).astype(np.uint8), wrap, dtype)
+        s0 = np.where(at0[..., None], levels[k]["texels"], s0)
+        s1 = np.where(at1[..., None], levels[k]["texels"], s1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mixed = s0 * omf[..., None] + s1 * f[..., None]
+    texels = np.where(valid[..., None], np.where(blend[..., None], mixed, s0), dt(0))
+    assert texels.dtype == dt
+    out.update(texels=texels, valid=valid, k0=k0, k1=k1, f=f, omf=omf, blend=blend, levels=levels)
+    return out
+
+
+def sample_mip_vjp(chain, grad, fwd):
+    """-> dict: grad_packed, n, S ([N,C] or [Tf,N,C], float64 / int64 / float64), grad_uv, abs_uv [B,H,W,2]"""
+    L = len(chain)
+    g = np.asarray(grad, np.float64)
+    f, omf = fwd["f"].astype(np.float64), fwd["omf"].astype(np.float64)
+    gp, n, S = [], [], []
+    guv, auv = np.zeros(fwd["valid"].shape + (2,)), np.zeros(fwd["valid"].shape + (2,))
+    for k in range(L):
+        t = np.asarray(chain[k], np.float64)
+        if k not in fwd["levels"]:
+            gp.append(np.zeros(t.shape)), n.append(np.zeros(t.shape, np.int64)), S.append(np.zeros(t.shape))
+            continue
+        at0, at1 = fwd["valid"] & (fwd["k0"] == k), fwd["blend"] & (fwd["k1"] == k)
+        wl = np.where(at0, np.where(fwd["blend"], omf, 1.0), 0.0) + np.where(at1, f, 0.0)
+        v = tc.sample_vjp(t, g * wl[..., None], fwd["levels"][k])
+        gp.append(v["grad_texture"]), n.append(v["n"]), S.append(v["S"])
+        guv += v["grad_uv"]
+        auv += v["abs_uv"]
+    return {"grad_packed": pack(gp), "n": pack(n), "S": pack(S), "grad_uv": guv, "abs_uv": auv}
+
+
+# ---- bounds (2^-24: the unit roundoff of float32)
+#
+# grad_packed.  One term, g * w1 * w2 * wl with the float32 weights the statement hands over, is three float32
+# products: k = 3 roundings (texture_cases counts 2 for g * w1 * w2; the level weight is one more; with f == 0 the
+# last product is by 1 and exact).  n terms are summed by n - 1 additions in any order, each rounding a partial sum of
+# at most S (1 + O(2^-24)); the n-th unit absorbs the second-order terms.
+K_PACKED = 3
+
+
+def packed_bound(vjp):
+    return (vjp["n"] + K_PACKED) * 2.0 ** -24 * vjp["S"]
+
+
+# grad_uv.  Each level's grad_u (grad_v) is texture_cases' C + 5 roundings of its absolute terms A_k; its product with
+# the level weight is one more rounding and the sum of the two levels' products another: C + 7 units of
+# |1-f| A_k0 + |f| A_k1, which is what sample_mip_vjp accumulates in abs_uv.  With f == 0 the last two do not happen.
+def uv_bound(vjp, C):
+    return (tc.uv_roundings(C) + 2) * 2.0 ** -24 * vjp["abs_uv"]
+
+
+# grad_texture, end to end.  The exact value of an element is sum_k W_k g_k (g_k the level-k element above it, W_k the
+# product of the box weights below level k: chain_weights).  The gather multiplies by 0.25 or 0.5, which is exact, and
+# adds L - 1 times; each addition rounds a partial sum of at most sum_k W_k |g~_k|, g~_k the float32 level gradients it
+# reads, |g~_k| <= S_k + packed_bound_k.  Their own errors arrive weighted: sum_k W_k (n_k + 3) 2^-24 S_k.  Together,
+# with the L-th unit absorbing the second-order terms:  sum_k W_k (n_k + 3 + L) 2^-24 S_k.
+def texture_bound(vjp, Th, Tw, levels=None):
+    dims, _, _ = layout(Th, Tw, levels)
+    L = len(dims)
+    per_level = (vjp["n"] + K_PACKED + L) * 2.0 ** -24 * vjp["S"]
+    scaled = [W * lv for W, lv in zip(chain_weights(Th, Tw, levels), unpack(per_level, Th, Tw, levels))]
+    # the same gather with weights already applied: plain sums of the levels above each element
+    i, j = np.arange(Th)[:, None], np.arange(Tw)[None, :]
+    return sum(lv[..., i >> k, j >> k, :] for k, lv in enumerate(scaled))
+
+
+# ---- the table
+
+FRAMES = {"1x1": (1, 1, 1), "1x2": (1, 1, 2), "2x1": (1, 2, 1), "15x17": (1, 15, 17), "16x16": (1, 16, 16),
+          "17x33": (1, 17, 33), "3x5x6": (3, 5, 6)}
+TEXTURES = [(1, 1), (2, 2), (4, 2), (1, 8), (8, 8), (6, 10), (5, 7), (64, 64)]
+CHANNELS = [1, 3, 4, 8]
+
+
+def _uv_minify(sx, sy):
+    """a smooth warp moving sx texels per pixel in x and sy in y (a few percent of wobble): rho2 about max(sx, sy)^2"""
+    def make(shape, Th, Tw, rng):
+        y, x = tc._yx(shape)
+        u = 0.11 + sx * (x + 0.04 * np.sin(y / 3.0)) / Tw
+        v = 0.07 + sy * (y + 0.04 * np.cos(x / 4.0)) / Th
+        return np.stack([u, v], -1)
+    return make
+
+
+def _uv_zoom(shape, Th, Tw, rng):
+    """the step grows from 0.5 to about 6 texels across the frame: a 16 x 16 tile holds several levels"""
+    y, x = tc._yx(shape)
+    u = 0.02 + (0.5 * x + 0.085 * x * x) / Tw
+    v = 0.03 + (0.5 * y + 0.085 * y * y) / Th
+    return np.stack([u, v], -1)
+
+
+UV_FAMILIES = {"min1": _uv_minify(1, 1), "min2": _uv_minify(2, 2), "min3": _uv_minify(3, 3), "min4": _uv_minify(4, 4),
+               "min8": _uv_minify(8, 8), "aniso": _uv_minify(4, 1), "zoom": _uv_zoom, "random": tc._uv_random,
+               "seam": tc._uv_seam, "extreme": tc._uv_extreme}
+SMOOTH = ("min1", "min2", "min3", "min4", "min8", "aniso", "random")
+
+
+def _holes(shape, rng):
+    """True = sampled.  Random holes, and where the frame allows it a sampled pixel whose four neighbours are holes
+    (difference branch 2 in both axes), one with only its left and upper neighbours (branch 1), at (1,1) and (3,3)."""
+    B, H, W = shape
+    covered = rng.random(shape) < 0.7
+    if H >= 5 and W >= 5:
+        covered[:, 0:3, 0:3] = False
+        covered[:, 1, 1] = True
+        covered[:, 2:5, 2:5] = False
+        covered[:, 3, 3] = covered[:, 3, 2] = covered[:, 2, 3] = True
+    return covered
+
+
+# (id, frame, texture size, C, per-frame chain, uv family, wrap, holes, lod mode, lod_bias, levels)
+# holes: None, "bg" (-inf background, sampled = finite), "mask" (an explicit mask besides the background)
+# lod mode: "auto", "int" (an explicit integer-valued lod, with a NaN), "frac" (an explicit fractional lod beyond both
+# ends of the chain)
+def _table():
+    rows = []
+
+    def add(frame, tex, C, per_frame, family, wrap, holes=None, mode="auto", bias=0.0, levels=None):
+        ident = "%s-t%dx%d-c%d-%s-%s-%s-%s%s%s%s" % (
+            frame, tex[0], tex[1], C, "perframe" if per_frame else "shared", family, wrap, mode,
+            "-" + holes if holes else "", "-bias%+.2f" % bias if bias else "", "-l%d" % levels if levels else "")
+        rows.append((ident, frame, tex, C, per_frame, family, wrap, holes, mode, bias, levels))
+
+    # every frame x every texture, everything else cycling
+    k = 0
+    for frame in FRAMES:
+        for tex in TEXTURES:
+            add(frame, tex, CHANNELS[k % 4], frame == "3x5x6" and k % 2 == 1, SMOOTH[k % len(SMOOTH)], WRAPS[k % 2],
+                (None, "bg", "mask")[k % 3], ("auto", "auto", "int", "auto", "frac")[k % 5],
+                (0.0, 0.0, 0.7, 0.0, -0.6, 0.0, 0.0)[k % 7])
+            k += 1
+    # the 64 x 64 chain (7 levels) under every family, on one tile, on several, and on the batch
+    for frame in ("16x16", "17x33", "3x5x6"):
+        per_frame = frame == "3x5x6"
+        for n, family in enumerate(UV_FAMILIES):
+            add(frame, (64, 64), CHANNELS[n % 4], per_frame, family, WRAPS[n % 2], ("bg", None)[n % 2])
+        add(frame, (64, 64), 3, per_frame, "min2", "repeat", "mask", "int")
+        add(frame, (64, 64), 3, per_frame, "min2", "clamp", "bg", "frac")
+        add(frame, (64, 64), 4, per_frame, "min4", "clamp", None, "auto", 1.3)
+        add(frame, (64, 64), 4, per_frame, "min4", "repeat", "bg", "auto", -1.25)
+        add(frame, (64, 64), 3, per_frame, "min8", "clamp", "bg", "auto", 0.0, 3)
+    # every channel count on the frame with several tiles, both wraps, holes; the other chains' seams and extremes
+    for C in CHANNELS:
+        add("17x33", (8, 8), C, False, "zoom", "clamp", "bg")
+        add("17x33", (6, 10), C, False, "min2", "repeat", "mask", "frac")
+    for tex in ((8, 8), (6, 10), (4, 2), (1, 8), (5, 7)):
+        add("15x17", tex, 3, False, "seam", "repeat")
+        add("15x17", tex, 3, False, "extreme", "clamp", "bg")
+    return rows
+
+
+TABLE = _table()
+CASE_IDS = [r[0] for r in TABLE]
+assert len(set(CASE_IDS)) == len(CASE_IDS)
+_ROWS = {r[0]: r for r in TABLE}
+
+
+@functools.lru_cache(maxsize=None)
+def case_input(ident):
+    """dict: texture float32 ([Th,Tw,C] or [B,Th,Tw,C]), uv float32 [B,H,W,2], mask uint8 [B,H,W] or None, wrap, lod
+    float32 [B,H,W] or None, lod_bias, levels, grad float32 [B,H,W,C]"""
+    _, frame, (Th, Tw), C, per_frame, family, wrap, holes, mode, bias, levels = _ROWS[ident]
+    shape = FRAMES[frame]
+    rng = tc._rng(ident)
+    texture = rng.standard_normal(((shape[0],) if per_frame else ()) + (Th, Tw, C)).astype(F32)
+    uv = np.ascontiguousarray(UV_FAMILIES[family](shape, Th, Tw, rng), F32)
+    mask = None
+    if holes:
+        uv[~_holes(shape, rng)] = -np.inf
+        flat = uv.reshape(-1, 2)
+        if len(flat) >= 64:  # a NaN and a +inf in one channel only
+            flat[7, 0] = np.nan
+            flat[len(flat) // 2, 1] = np.inf
+        if holes == "mask":
+            finite = np.isfinite(uv).all(-1)
+            mask = (finite & (rng.random(shape) < 0.8)).astype(np.uint8)
+    L = len(layout(Th, Tw, levels)[0])
+    lod = None
+    if mode == "int":
+        lod = rng.integers(-1, L + 1, shape).astype(F32)
+        lod.reshape(-1)[0] = np.nan
+    elif mode == "frac":
+        lod = rng.uniform(-0.5, L - 0.5, shape).astype(F32)
+        lod.reshape(-1)[-1] = np.inf
+    grad = rng.standard_normal(shape + (C,)).astype(F32)
+    return dict(texture=texture, uv=uv, mask=mask, wrap=wrap, lod=lod, lod_bias=bias, levels=levels, grad=grad)
+
+
+def statement(inp, dtype=F32):
+    """(chain, forward dict, vjp dict with grad_texture and its bound besides) of the statement for case_input's dict"""
+    chain = build_chain(inp["texture"], inp["levels"], dtype)
+    fwd = sample_mip(chain, inp["uv"], inp["mask"], inp["wrap"], inp["lod"], inp["lod_bias"], dtype)
+    vjp = sample_mip_vjp(chain, inp["grad"], fwd)
+    Th, Tw = chain[0].shape[-3:-1]
+    vjp["grad_texture"] = chain_vjp(vjp["grad_packed"], Th, Tw, inp["levels"])
+    vjp["texture_bound"] = texture_bound(vjp, Th, Tw, inp["levels"])
+    return chain, fwd, vjp
+
+
+@functools.lru_cache(maxsize=None)
+def case(ident):
+    """(inputs, chain, forward dict, vjp dict) of the float32 statement: computed once per process, read-only"""
+    inp = case_input(ident)
+    return (inp,) + statement(inp)
+
+
+# ---- the exact scatter: every coordinate on a half texel of both levels it reads, f in {0, 1/2}, small integer
+# cotangents and texels: every product and partial sum is exact in float32, whatever the order of the atomics
+
+@functools.lru_cache(maxsize=None)
+def exact_scatter_case(kind, C=3, frames=1):
+    """kind 'magnify': one texel step every 16 pixels; 'scatter': random positions over the 64 x 64 texture"""
+    shape, T = (frames, 33, 35), 64
+    rng = tc._rng("mipexact", kind, C, frames)
+    if kind == "magnify":
+        y, x = tc._yx(shape)
+        ku, kv = 9 + (x // 16).astype(np.int64), 13 + (y // 16).astype(np.int64)
+    else:
+        ku, kv = rng.integers(1, T // 4, shape), rng.integers(1, T // 4, shape)
+    # u = k / 16: x_k = 64 u / 2^k - 0.5 = 4 k / 2^k - 0.5 has fraction 1/2 at the levels 0..2, 0 at level 3
+    uv = np.stack([ku / 16.0, kv / 16.0], -1).astype(F32)
+    uv[:, 3, 4] = -np.inf
+    lod = (rng.integers(0, 6, shape) / 2.0).astype(F32)  # 0, 0.5, .., 2.5: levels 0..3
+    texture = rng.integers(-2, 3, (T, T, C)).astype(F32) * 64.0
+    grad = rng.integers(-3, 4, shape + (C,)).astype(F32)
+    inp = dict(texture=texture, uv=uv, mask=None, wrap="clamp", lod=lod, lod_bias=0.0, levels=None, grad=grad)
+    chain, fwd, vjp = statement(inp)
+    for lv in fwd["levels"].values():
+        assert set(np.unique(lv["a"])) <= {0.0, 0.5} and set(np.unique(lv["b"])) <= {0.0, 0.5}
+    assert set(np.unique(fwd["f"])) == {0.0, 0.5}
+    return inp, chain, fwd, vjp
+
+
+# ---- coverage conditions, asserted at import so that the table cannot quietly miss them
+
+def _coverage():
+    k0_seen, f_zero, f_frac, tiles_mixed = set(), False, False, False
+    bx, by = set(), set()
+    for ident in CASE_IDS:
+        row = _ROWS[ident]
+        inp, _, fwd, _ = case(ident)
+        v = fwd["valid"]
+        if row[8] == "auto":
+            bx |= set(np.unique(fwd["branch_x"][v]).tolist())
+            by |= set(np.unique(fwd["branch_y"][v]).tolist())
+        if row[2] != (64, 64) or row[10] is not None:
+            continue
+        k0_seen |= set(np.unique(fwd["k0"][v]).tolist())
+        f_zero |= bool((fwd["f"][v] == 0).any())
+        f_frac |= bool(((fwd["f"][v] > 0) & (fwd["f"][v] < 1)).any())
+        B, H, W = v.shape
+        for b in range(B):
+            for ty in range(0, H, 16):
+                for tx in range(0, W, 16):
+                    sl = (b, slice(ty, ty + 16), slice(tx, tx + 16))
+                    tiles_mixed |= len(np.unique(fwd["k0"][sl][v[sl]])) >= 2
+    assert k0_seen == set(range(7)), k0_seen
+    assert f_zero and f_frac and tiles_mixed
+    assert bx == {0, 1, 2} and by == {0, 1, 2}, (bx, by)
+
+
+_coverage()
