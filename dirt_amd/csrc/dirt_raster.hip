@@ -953,6 +953,20 @@ int dirt_debug_bin_occupancy(int B, int H, int W, int F, int64_t bin_capacity, c
     return DIRT_OK;
 }
 
+// Debug: the current device's hipDeviceAttributeMaxGridDimY, or 0 where it cannot be read.  The batch B is grid.y of
+// the setup, raster, grad and vertex-normal launches; launches beyond the attribute's 65536 run on an MI355X
+// (tests/test_gpu_large_frames.py renders 65537 frames, tests/test_gpu_lighting_f64.py 70,000), so nothing is
+// refused by it.  Not part of include/dirt_mi355x.h.
+int dirt_debug_max_grid_y(void)
+{
+    int dev = 0, lim = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxGridDimY, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return lim;
+}
+
 // Debug (synchronises `stream`): the R5 deviation counters of `scratch` (setup_kernel.h kStatCapCulled /
 // kStatClamped), summed over every forward since the scratch was last cleared: faces culled by the R5 vertex cap
 // and clipped faces whose sub-vertices the R5 clamp moved.  reset != 0 zeroes them afterwards.  Not part of

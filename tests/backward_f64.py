@@ -24,7 +24,7 @@ The visible record of each pixel (the forward's g-buffer) is an input: visibilit
 pinned separately -- coverage by tests/exact_cover.py, depth, clipping, the visible record and the forward's
 values by tests/forward_exact.py (exact plane depth with derived float32 bounds; the oracle against it in
 tests/test_forward_exact.py, the HIP kernels in tests/test_gpu_forward_exact.py).  Pure-Python loops: small
-frames only.
+frames, or a small window of a large one (`window`).
 
 backward_with_bounds / backward_batch_with_bounds return the same values and, per element, the sum of the absolute
 values of its terms and their number (Bounds): what the per-element contract of tests/backward_cases.py is stated in.
@@ -187,19 +187,50 @@ def _record(tris, F, ri):
     return f, tris[f][0][d - f * EXTRA_PER_FACE + 1]
 
 
-def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None):
+def _supported_on(grad_pixels, window):
+    """Whether grad_pixels [H,W,C] is zero outside window (i0, i1, j0, j1) (window coordinates, inclusive)."""
+    i0, i1, j0, j1 = window
+    H = grad_pixels.shape[0]
+    return np.count_nonzero(grad_pixels) == np.count_nonzero(grad_pixels[H - 1 - j1:H - j0, i0:i1 + 1])
+
+
+def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None, window=None):
     """One frame: vertices [V,4], faces [F,3], pixels / grad_pixels [H,W,C] (rows top first), gbuffer [H,W]
     (visible record, bit 30 = clipped face, -1 background).  Returns float64 (grad_vertices [V,4],
-    grad_vertex_colors [V,C], grad_background [H,W,C]).  track: a Bounds to fill next to them (backward_with_bounds)."""
+    grad_vertex_colors [V,C], grad_background [H,W,C]).  track: a Bounds to fill next to them (backward_with_bounds).
+
+    window = (i0, i1, j0, j1), window coordinates, inclusive: grad_pixels must be zero outside it (asserted).  Then
+    every colour term outside the window and every pair with neither pixel inside it has G = 0 as a factor and is
+    exactly zero, so the colour loop visits the window and the pair loop the window and its one-pixel halo, in the
+    dense order; pixels are converted one at a time and nothing of the frame's size is allocated.  Returns
+    (grad_vertices, grad_vertex_colors, None): grad_background is the cotangent on uncovered pixels, a statement
+    about the g-buffer alone.  S, n, N and clip of `track` count the window's terms -- the only non-zero ones."""
     H, W, C = pixels.shape
     V, F = vertices.shape[0], faces.shape[0]
     tris = [setup_face(vertices, faces[f], V, W, H) for f in range(F)]
-    I = pixels.astype(np.float64)
-    G = grad_pixels.astype(np.float64)
     gv = np.zeros((V, 4))
     gc = np.zeros((V, C))
-    gbg = np.zeros((H, W, C))
-    rec = np.where(gbuffer < 0, -1, gbuffer & (GBUF_MULTI - 1))
+    if window is None:
+        I = pixels.astype(np.float64)
+        G = grad_pixels.astype(np.float64)
+        gbg = np.zeros((H, W, C))
+        rec = np.where(gbuffer < 0, -1, gbuffer & (GBUF_MULTI - 1))
+        ci0, ci1, cj0, cj1 = pi0, pi1, pj0, pj1 = 0, W - 1, 0, H - 1
+    else:
+        class _PerPixel:  # float64 / the record index of one pixel at a time
+            def __init__(self, a, conv):
+                self.a, self.conv = a, conv
+
+            def __getitem__(self, rc):
+                return self.conv(self.a[rc])
+        ci0, ci1, cj0, cj1 = (int(x) for x in window)
+        assert 0 <= ci0 <= ci1 < W and 0 <= cj0 <= cj1 < H, window
+        assert _supported_on(grad_pixels, (ci0, ci1, cj0, cj1)), "grad_pixels is not zero outside the window"
+        I = _PerPixel(pixels, lambda x: x.astype(np.float64))
+        G = _PerPixel(grad_pixels, lambda x: x.astype(np.float64))
+        gbg = None
+        rec = _PerPixel(gbuffer, lambda x: -1 if x < 0 else int(x) & (GBUF_MULTI - 1))
+        pi0, pi1, pj0, pj1 = max(ci0 - 1, 0), ci1, max(cj0 - 1, 0), cj1
 
     def at(i, j):  # window (i, j) -> image row
         return H - 1 - j, i
@@ -207,11 +238,12 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None):
     def face_covers(f, i, j):
         return any(t is not None and t.covers(i, j) for t in tris[f][0])
 
-    for j in range(H):
-        for i in range(W):
+    for j in range(cj0, cj1 + 1):
+        for i in range(ci0, ci1 + 1):
             r = rec[at(i, j)]
             if r < 0:
-                gbg[at(i, j)] = G[at(i, j)]
+                if gbg is not None:
+                    gbg[at(i, j)] = G[at(i, j)]
                 continue
             f, t = _record(tris, F, int(r))
             lam, _ = t.weights([2 * e for e in t.E(256 * i + 128, 256 * j + 128)])
@@ -221,7 +253,7 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None):
                 track.colour(faces[f], t, [2 * e for e in t.E(256 * i + 128, 256 * j + 128)], lam, G[at(i, j)],
                              tris[f][1], (i, j))
 
-    def add(ri, i, j, axis, s, omega, s_abs=0.0):
+    def add(ri, i, j, axis, s, omega, s_abs=0.0, own_low=True):
         f, t = _record(tris, F, int(ri))
         if axis == 0:
             E2 = [t.A[k] * (512 * i + 512) + t.B[k] * (512 * j + 256) + 2 * t.C[k] for k in range(3)]
@@ -236,10 +268,10 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None):
             gv[faces[f][k], 3] -= g * ndc
         if track is not None:
             track.pair(faces[f], t, E2, axis, omega, s, s_abs, half, ndc, [lam[k] / Wm for k in range(3)], tris[f][1],
-                       (i, j), int(ri))
+                       (i, j), int(ri), own_low)
 
-    for j in range(H):
-        for i in range(W):
+    for j in range(pj0, pj1 + 1):
+        for i in range(pi0, pi1 + 1):
             for axis in (0, 1):
                 i2, j2 = (i + 1, j) if axis == 0 else (i, j + 1)
                 if i2 >= W or j2 >= H:
@@ -260,25 +292,27 @@ def backward(vertices, faces, pixels, grad_pixels, gbuffer, track=None):
                 if fp == fq or fq < 0:
                     add(rp, i, j, axis, s, 1.0, sa)
                 elif fp < 0:
-                    add(rq, i, j, axis, s, 1.0, sa)
+                    add(rq, i, j, axis, s, 1.0, sa, False)
                 else:
                     p_covers_q, q_covers_p = face_covers(fp, i2, j2), face_covers(fq, i, j)
                     if not p_covers_q and q_covers_p:
                         add(rp, i, j, axis, s, 1.0, sa)
                     elif p_covers_q and not q_covers_p:
-                        add(rq, i, j, axis, s, 1.0, sa)
+                        add(rq, i, j, axis, s, 1.0, sa, False)
                     else:
                         add(rp, i, j, axis, s, 0.5, sa)
-                        add(rq, i, j, axis, s, 0.5, sa)
+                        add(rq, i, j, axis, s, 0.5, sa, False)
     return gv, gc, gbg
 
 
-def backward_batch(vertices, faces, pixels, grad_pixels, gbuffer):
-    outs = [backward(vertices[b], faces[b], pixels[b], grad_pixels[b], gbuffer[b]) for b in range(pixels.shape[0])]
-    return tuple(np.stack([o[k] for o in outs]) for k in range(3))
+def backward_batch(vertices, faces, pixels, grad_pixels, gbuffer, window=None):
+    outs = [backward(vertices[b], faces[b], pixels[b], grad_pixels[b], gbuffer[b], None, window)
+            for b in range(pixels.shape[0])]
+    return tuple(None if outs[0][k] is None else np.stack([o[k] for o in outs]) for k in range(3))
 
 
 U32 = 2.0 ** -24  # float32's unit roundoff (round to nearest)
+INT64_EDGE = 1 << 14  # grad_kernel.h kGradSmallEdge: records with |A_k| or |B_k| from here on take int64 edge values
 
 
 class Bounds:
@@ -296,6 +330,13 @@ class Bounds:
                               |basis_ki|: the dL/dx and dL/dy terms whose product with the float32 x_ndc the w
                               component is -- x_ndc = mid (2 / W) - 1 carries an absolute rounding error, not one
                               relative to |x_ndc|;
+      L_v [V,4]               sum of E_k(o) |d term / d E_k(o)| over the element's pair terms on records with an edge
+                              coefficient |A_k| or |B_k| of at least INT64_EDGE, and of those over the sub-vertices k
+                              with |E2_k| < 2 E_k(o) -- o the pixel of the pair that shows the owning record,
+                              E2_k = 2 E_k(o) +- one pixel's step: what a rounding of E_k(o) that is relative to
+                              E_k(o) costs the element where E_k(o) exceeds half the midpoint value.  Where
+                              |E2_k| >= 2 E_k(o) such a rounding is within the same rounding of E2_k and the count
+                              of tests/backward_cases.py holds as it stands: nothing is added;
       terms                   (keep_terms) every term as a dict, for tests that rebuild wrong sums from them.
     Pairs the specification skips (a non-finite background on either side, s == 0) add nothing."""
 
@@ -303,13 +344,24 @@ class Bounds:
         self.S_v, self.n_v = np.zeros((V, 4)), np.zeros((V, 4), np.int64)
         self.S_c, self.n_c = np.zeros((V, C)), np.zeros((V, C), np.int64)
         self.N_v = np.zeros((V, 4))
+        self.L_v = np.zeros((V, 4))
         self.clip_v, self.clip_c = np.zeros((V, 4), bool), np.zeros((V, C), bool)
         self.terms = [] if keep_terms else None
         self.n_half = 0  # pair owners with weight 0.5
 
-    def pair(self, f3, t, E2, axis, omega, s, s_abs, half, ndc, lam_w, clipped, pixel, ri):
+    def pair(self, f3, t, E2, axis, omega, s, s_abs, half, ndc, lam_w, clipped, pixel, ri, own_low=True):
         aw, _ = t.abs_weights(E2)
         self.n_half += omega == 0.5
+        # E_k at the owner's pixel, exactly: E2_k = 2 E_k(low) + step = 2 E_k(high) - step, step = 256 A_k (256 B_k)
+        step = [256 * (t.A[k] if axis == 0 else t.B[k]) for k in range(3)]
+        Eo = [(E2[k] - step[k]) // 2 if own_low else (E2[k] + step[k]) // 2 for k in range(3)]
+        if max(abs(x) for x in t.A + t.B) >= INT64_EDGE:
+            # d term_i / d E_k(o) = omega s half basis_ki / (D w_k) (E2_k / 2D with E2_k = 2 E_k(o) +- step)
+            for i in range(3):
+                la = omega * s_abs * half * sum(abs(Eo[k]) / (t.D * t.w[k]) * abs(t.basis[k][i]) for k in range(3)
+                                                if abs(E2[k]) < 2 * abs(Eo[k]))
+                self.L_v[int(f3[i]), axis] += la
+                self.L_v[int(f3[i]), 3] += la * abs(ndc)
         for k in range(3):
             v = int(f3[k])
             g, ga = omega * s * half * lam_w[k], omega * s_abs * half * aw[k]
@@ -320,7 +372,7 @@ class Bounds:
             self.N_v[v, 3] += ga
             if self.terms is not None:
                 self.terms.append(dict(kind="pair", vertex=v, axis=axis, pixel=pixel, record=ri, omega=omega, g=g,
-                                       ndc=ndc, abs=ga))
+                                       ndc=ndc, abs=ga, E2=list(E2), E_owner=Eo, own_low=own_low))
 
     def colour(self, f3, t, E2, lam, G, clipped, pixel):
         _, ac = t.abs_weights(E2)
@@ -334,17 +386,18 @@ class Bounds:
                 self.terms.append(dict(kind="colour", vertex=v, pixel=pixel, g=val))
 
 
-def backward_with_bounds(vertices, faces, pixels, grad_pixels, gbuffer, keep_terms=False):
+def backward_with_bounds(vertices, faces, pixels, grad_pixels, gbuffer, keep_terms=False, window=None):
     """`backward` (the same values, bit for bit) and the Bounds of its elements."""
     track = Bounds(vertices.shape[0], pixels.shape[2], keep_terms)
-    return backward(vertices, faces, pixels, grad_pixels, gbuffer, track) + (track,)
+    return backward(vertices, faces, pixels, grad_pixels, gbuffer, track, window) + (track,)
 
 
-def backward_batch_with_bounds(vertices, faces, pixels, grad_pixels, gbuffer, keep_terms=False):
-    """`backward_batch` and one Bounds per frame."""
-    outs = [backward_with_bounds(vertices[b], faces[b], pixels[b], grad_pixels[b], gbuffer[b], keep_terms)
+def backward_batch_with_bounds(vertices, faces, pixels, grad_pixels, gbuffer, keep_terms=False, window=None):
+    """`backward_batch` and one Bounds per frame (window: the same one in every frame; grad_background None)."""
+    outs = [backward_with_bounds(vertices[b], faces[b], pixels[b], grad_pixels[b], gbuffer[b], keep_terms, window)
             for b in range(pixels.shape[0])]
-    return tuple(np.stack([o[k] for o in outs]) for k in range(3)) + ([o[3] for o in outs],)
+    return tuple(None if outs[0][k] is None else np.stack([o[k] for o in outs]) for k in range(3)) + (
+        [o[3] for o in outs],)
 
 
 def stack_bounds(bounds, name):

@@ -88,10 +88,18 @@ def quantise(zw):
 class Frame:
     """The statement of one frame: per covering (pixel, record) pair, flat arrays sorted by nothing in
     particular -- pix (window j * W + i), rec, face, key (face * 8 + s), z (float64 of z*), S, d_lo, d_hi,
-    certain, possible, winner -- and per pixel `winners[j][i]`, the list of pair indices that may be visible."""
+    certain, possible, winner -- and per pixel `winners[j][i]`, the list of pair indices that may be visible.
 
-    def __init__(self, vertices, faces, W, H, record=None):
+    window = (i0, i1, j0, j1), window coordinates, inclusive: the statement of those pixels only.  Record bounding
+    boxes are intersected with it, `pix` is (j - j0) * (i1 - i0 + 1) + (i - i0) and the per-pixel tables (winners,
+    any_certain, covered) are window-sized and indexed [j - j0][i - i0]; nothing of the frame's size is allocated,
+    so the frame may be 8192x8192.  None is the whole frame."""
+
+    def __init__(self, vertices, faces, W, H, record=None, window=None):
         self.W, self.H = W, H
+        self.window = i0, i1, j0, j1 = (0, W - 1, 0, H - 1) if window is None else tuple(int(x) for x in window)
+        assert 0 <= i0 <= i1 < W and 0 <= j0 <= j1 < H, self.window
+        self.ww, self.wh = i1 - i0 + 1, j1 - j0 + 1
         self.vertices, self.faces = vertices, faces
         V, F = vertices.shape[0], faces.shape[0]
         self.F = F
@@ -115,9 +123,9 @@ class Frame:
         self._resolve()
 
     def _add_record(self, cols, ri, f, s, t, triple_ids):
-        W, H = self.W, self.H
-        i0, i1 = max(0, (min(t.X) - 128 + 255) // 256), min(W - 1, (max(t.X) - 128) // 256)
-        j0, j1 = max(0, (min(t.Y) - 128 + 255) // 256), min(H - 1, (max(t.Y) - 128) // 256)
+        wi0, wi1, wj0, wj1 = self.window
+        i0, i1 = max(wi0, (min(t.X) - 128 + 255) // 256), min(wi1, (max(t.X) - 128) // 256)
+        j0, j1 = max(wj0, (min(t.Y) - 128 + 255) // 256), min(wj1, (max(t.Y) - 128) // 256)
         if i0 > i1 or j0 > j1:
             return
         inside, E = t.covers_grid(i0, i1, j0, j1)
@@ -126,7 +134,7 @@ class Frame:
         jj, ii = np.nonzero(inside)
         n = len(ii)
         ii, jj = ii + i0, jj + j0
-        cols["pix"].append(jj * W + ii)
+        cols["pix"].append((jj - wj0) * self.ww + (ii - wi0))
         cols["rec"].append(np.full(n, ri))
         cols["face"].append(np.full(n, f))
         cols["key"].append(np.full(n, f * 8 + s))
@@ -176,7 +184,7 @@ class Frame:
         cols["flat"].append(np.zeros(n, bool))
 
     def _resolve(self):
-        W, H, n = self.W, self.H, self.n
+        W, H, n = self.ww, self.wh, self.n  # (the window's size: the per-pixel tables cover the window only)
         big = np.int64(1) << 62
         # per pixel: the smallest d_hi over the records certainly in range, and the lowest key among those
         m = np.full(W * H, big)
@@ -210,7 +218,7 @@ class Frame:
         """Of pair a: exact barycentrics, their bounds, colours [C], their bounds (float64)."""
         f, s, t, clipped = self.rec_tri[int(self.rec[a])]
         p = int(self.pix[a])
-        i, j = p % self.W, p // self.W
+        i, j = self.window[0] + p % self.ww, self.window[2] + p // self.ww
         E = t.E(256 * i + 128, 256 * j + 128)
         lam, _ = t.weights([2 * e for e in E])
         q = [E[k] / t.w[k] for k in range(3)]
@@ -225,14 +233,16 @@ def check_frame(fr, background, colours, pixels, gbuffer=None, depth=None, baryc
     """Every assertion of the pin on one frame's outputs (rows top first; depth, barycentrics and one of gbuffer /
     face_ids may be None).  Returns the figures: worst |error| / (u sum |terms|) for depth (a lower bound of it,
     from d alone), barycentrics and colours -- to compare with K_DEPTH, K_BARY, K_COLOUR -- and the counts of
-    covered and undecided pixels."""
-    W, H, F = fr.W, fr.H, fr.F
+    covered and undecided pixels.  A windowed Frame: the outputs are the whole frame's, the window's pixels are
+    visited and counted."""
+    H = fr.H
+    i0, i1, j0, j1 = fr.window
     worst = {"depth": 0.0, "barycentrics": 0.0, "colours": 0.0}
     undecided = 0
-    for j in range(H):
+    for j in range(j0, j1 + 1):
         r = H - 1 - j
-        for i in range(W):
-            win = fr.winners[j][i]
+        for i in range(i0, i1 + 1):
+            win = fr.winners[j - j0][i - i0]
             undecided += len(win) > 1
             where = "pixel (%d, %d)" % (i, j)
             seen_face = None
@@ -250,7 +260,7 @@ def check_frame(fr, background, colours, pixels, gbuffer=None, depth=None, baryc
             elif face_ids[r, i] >= 0:
                 seen_face = int(face_ids[r, i])
             if seen_face is None:
-                assert not fr.any_certain[j, i], "%s: background, but a record is certainly in range" % where
+                assert not fr.any_certain[j - j0, i - i0], "%s: background, but a record is certainly in range" % where
                 assert np.array_equal(pixels[r, i].view(np.uint32), background[r, i].view(np.uint32)), where
                 if depth is not None:
                     assert depth[r, i] == np.float32(1.0), where
