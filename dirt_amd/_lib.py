@@ -35,6 +35,7 @@ FWD_DEEP_CULL_OFF = 8  # dirt_rasterise_fwd: never the occluder culling
 TEXTURE_CLAMP = 0      # dirt_texture_sample_* wrap modes
 TEXTURE_REPEAT = 1
 MAX_MIP_LEVELS = 14    # dirt_texture_mip_*: the chain of an 8192 x 8192 texture
+MAX_LIGHTS = 8         # dirt_deferred_shade_lights_*
 BWD_ACCUMULATE = 1    # dirt_rasterise_bwd / dirt_rasterise_bwd_recompute flags
 BWD_SCRATCH_CLEAN = 2  # dirt_rasterise_bwd_recompute: the workspace's bin counters are clean
 
@@ -76,6 +77,11 @@ SIGNATURES = {
     "dirt_deferred_shade_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
     "dirt_deferred_shade_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P,
                                      _P, _P]),
+    "dirt_deferred_shade_lights_workspace": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "dirt_deferred_shade_lights_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _U, _I, _P, _P, _P, _I, _P, ctypes.c_float,
+                                            _P, _I, _P, _P, _P, _P]),
+    "dirt_deferred_shade_lights_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _U, _I, _P, _P, _P, _I, _P, ctypes.c_float,
+                                            _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dirt_texture_sample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dirt_texture_sample_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dirt_texture_mip_layout": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_longlong),

@@ -290,6 +290,7 @@ struct EventPair {
 #include "grad_kernel.h"
 #include "lighting_kernels.h"
 #include "deferred_kernels.h"
+#include "shade_lights_kernels.h"
 #include "texture_kernels.h"
 #include "texture_mip_kernels.h"
 
@@ -1538,6 +1539,121 @@ int dirt_deferred_shade_bwd(const float *positions, const float *colors, const f
                            double_sided};
     deferred_shade_bwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
         positions, colors, normals, H, W, n, L, grad_pixels, route, grad_positions, grad_colors, grad_normals);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- deferred shading with many lights and gradients to them (shade_lights_kernels.h)
+
+namespace {
+
+// the argument checks the three entry points share beyond deferred_sizes': DIRT_OK with *pixels = B * H * W
+int shade_lights_sizes(int B, int H, int W, int n_lights, unsigned point_mask, int64_t *pixels)
+{
+    const int rc = deferred_sizes("deferred_shade_lights", B, H, W, 3, pixels);
+    if (rc) return rc;
+    if (n_lights < 0 || n_lights > DIRT_MAX_LIGHTS) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "deferred_shade_lights: expects 0 <= lights <= %d", DIRT_MAX_LIGHTS);
+        return fail(DIRT_EINVAL, msg);
+    }
+    if (point_mask >> n_lights) return fail(DIRT_EINVAL, "deferred_shade_lights: point_mask has bits past the lights");
+    return DIRT_OK;
+}
+
+int64_t shade_lights_chunks(int H, int W) { return ((int64_t)H * W + kSlChunk - 1) / kSlChunk; }
+
+size_t shade_lights_workspace_bytes(int B, int H, int W, int n_lights)
+{
+    return (size_t)B * (size_t)shade_lights_chunks(H, W) * (size_t)(kSlFixedSums + kSlSumsPerLight * n_lights) *
+           sizeof(float);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_deferred_shade_lights_workspace(int B, int H, int W, int n_lights, size_t *bytes)
+{
+    int64_t n;
+    const int rc = shade_lights_sizes(B, H, W, n_lights, 0u, &n);
+    if (rc) return rc;
+    if (!bytes) return fail(DIRT_EINVAL, "deferred_shade_lights: null pointer");
+    *bytes = shade_lights_workspace_bytes(B, H, W, n_lights);
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_lights_fwd(const float *positions, const float *colors, const float *normals, int B, int H,
+                                   int W, const float *ambient_color, int n_lights, unsigned point_mask,
+                                   int lights_per_frame, const float *light_vectors, const float *diffuse_colors,
+                                   const float *specular_colors, int camera_per_frame, const float *camera_position,
+                                   float shininess_value, const float *shininess_ptr, int double_sided, float *pixels,
+                                   uint8_t *valid, uint32_t *route, void *stream_)
+{
+    int64_t n;
+    const int rc = shade_lights_sizes(B, H, W, n_lights, point_mask, &n);
+    if (rc || n == 0) return rc;
+    if (!positions || !colors || !normals || !pixels || !valid || !route ||
+        (n_lights > 0 && (!light_vectors || !diffuse_colors || !specular_colors || !camera_position)))
+        return fail(DIRT_EINVAL, "deferred_shade_lights: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeLightsArgs A = {ambient_color, light_vectors, diffuse_colors, specular_colors, camera_position,
+                               shininess_ptr, shininess_value, n_lights, point_mask, lights_per_frame != 0,
+                               camera_per_frame != 0, double_sided};
+    shade_lights_fwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        positions, colors, normals, H, W, n, A, pixels, valid, route);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, const float *normals, int B, int H,
+                                   int W, const float *ambient_color, int n_lights, unsigned point_mask,
+                                   int lights_per_frame, const float *light_vectors, const float *diffuse_colors,
+                                   const float *specular_colors, int camera_per_frame, const float *camera_position,
+                                   float shininess_value, const float *shininess_ptr, int double_sided,
+                                   const float *grad_pixels, const uint32_t *route, float *grad_positions,
+                                   float *grad_colors, float *grad_normals, float *grad_ambient,
+                                   float *grad_light_vectors, float *grad_diffuse_colors, float *grad_specular_colors,
+                                   float *grad_camera, float *grad_shininess, void *workspace, size_t workspace_bytes,
+                                   void *stream_)
+{
+    int64_t n;
+    const int rc = shade_lights_sizes(B, H, W, n_lights, point_mask, &n);
+    if (rc || n == 0) return rc;
+    if (n_lights == 0) grad_light_vectors = grad_diffuse_colors = grad_specular_colors = nullptr;  // (empty arrays)
+    const bool want_params = grad_ambient || grad_light_vectors || grad_diffuse_colors || grad_specular_colors ||
+                             grad_camera || grad_shininess;
+    if (!want_params && !grad_positions && !grad_colors && !grad_normals) return DIRT_OK;
+    if (!positions || !colors || !normals || !grad_pixels || !route ||
+        (n_lights > 0 && (!light_vectors || !diffuse_colors || !specular_colors || !camera_position)))
+        return fail(DIRT_EINVAL, "deferred_shade_lights: null pointer");
+    if (want_params && (!workspace || workspace_bytes < shade_lights_workspace_bytes(B, H, W, n_lights)))
+        return fail(DIRT_EINVAL, "deferred_shade_lights: workspace smaller than "
+                                 "dirt_deferred_shade_lights_workspace() reports");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeLightsArgs A = {ambient_color, light_vectors, diffuse_colors, specular_colors, camera_position,
+                               shininess_ptr, shininess_value, n_lights, point_mask, lights_per_frame != 0,
+                               camera_per_frame != 0, double_sided};
+    const int chunks = (int)shade_lights_chunks(H, W);  // (at most 8192^2 / 1024)
+    const dim3 grid((unsigned)chunks, (unsigned)std::min(B, 65535));
+    float *partial = static_cast<float *>(workspace);
+    if (want_params) {
+        shade_lights_bwd_kernel<true><<<grid, dim3(kSlThreads), 0, stream>>>(
+            positions, colors, normals, B, H, W, A, grad_pixels, route, grad_positions, grad_colors, grad_normals,
+            partial);
+        // the camera without lights, and the shininess without lights, receive exact zeros from the empty sums
+        const SlParamGrads G = {grad_ambient, grad_light_vectors, grad_diffuse_colors, grad_specular_colors,
+                                grad_camera, grad_shininess};
+        shade_lights_reduce_kernel<<<dim3((unsigned)(kSlFixedSums + kSlSumsPerLight * n_lights)), dim3(kSlThreads), 0,
+                                     stream>>>(partial, B, chunks, n_lights, lights_per_frame != 0,
+                                               camera_per_frame != 0, G);
+    } else {
+        shade_lights_bwd_kernel<false><<<grid, dim3(kSlThreads), 0, stream>>>(
+            positions, colors, normals, B, H, W, A, grad_pixels, route, grad_positions, grad_colors, grad_normals,
+            nullptr);
+    }
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }

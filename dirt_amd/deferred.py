@@ -7,6 +7,9 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
 
   dilate(x, mask=None)     [H,W,C] or [B,H,W,C]: the 3x3 max where mask is set (default: any channel is +-inf)
   shade(positions, colors, normals, ...) -> (pixels, valid)
+  shade_lights(positions, colors, normals, light_vectors, diffuse_colors, specular_colors, camera_position, shininess,
+               ambient_color=None, point=None, double_sided=False) -> (pixels, valid): shade under up to 8 directional
+                           or point lights, with gradients to the lights, the camera, the ambient colour, the shininess
   sample_texture(texture, uv, mask=None, wrap="clamp") -> (texels, valid): bilinear texture lookup at a uv G-buffer
   build_mipmaps(texture, levels=None) -> Mipmaps: the box-filtered mip chain, packed
   sample_texture_mip(mipmaps_or_texture, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0) -> (texels, valid):
@@ -21,6 +24,12 @@ the window gives NaN.  The fused backwards are gathers in a fixed order: their g
 to run.  They are kernels, not differentiable graphs: `create_graph=True` through them raises RuntimeError;
 DIRT_FUSED_DEFERRED=0 routes every call to the framework ops (double backward supported).
 
+shade_lights is the shade for an inverse renderer that fits the lighting, a camera pose or a material exponent
+(dirt_amd/csrc/shade_lights_kernels.h, C ABI dirt_deferred_shade_lights_*; the statement is `_shade_lights_ops`): N
+lights in one pass over the G-buffers, and parameters that need a gradient stay on the fused path.  Its backward is two
+launches: per-chunk partial sums of the per-pixel parameter terms, then their sum in a fixed order -- no float atomics,
+every gradient bit-identical from run to run.  `shade` itself is unchanged.
+
 sample_texture is the step between the two: UV -> texel, with gradients to the texture and through the uv into the
 geometry (dirt_amd/csrc/texture_kernels.h, C ABI dirt_texture_sample_*; the statement is `_sample_texture_ops`).  Its
 uv gradient is a gather in a fixed order too; its texture gradient is a scatter-add summed with float atomics (per
@@ -30,13 +39,15 @@ build_mipmaps and sample_texture_mip are its minification-safe form (dirt_amd/cs
 dirt_texture_mip_* / dirt_texture_sample_mip_*; the statements are `_build_mipmaps_ops`, `_sample_texture_mip_ops`),
 with the same eligibility and fallback.  The level of detail is a constant of the backward: it carries no gradient.
 """
+import ctypes
 import os
 
 import torch
 import torch.nn.functional as Fn
 
 from . import _lib
-from .lighting import _diffuse_directional_ops, _gpu_f32, _light_param, _specular_directional_ops
+from .lighting import (_diffuse_directional_ops, _diffuse_point_ops, _gpu_f32, _light_param,
+                       _specular_directional_ops)
 
 __all__ = ["dilate", "shade"]
 
@@ -198,6 +209,198 @@ def shade(positions, colors, normals, ambient_color, light_direction, diffuse_co
             return (pixels, valid) if positions.dim() == 4 else (pixels[0], valid[0])
     return _shade_ops(positions, colors, normals, ambient_color, light_direction, diffuse_color, specular_color,
                       camera_position, shininess, double_sided)
+
+
+# ---- shade_lights: many lights, with gradients to them
+
+def _specular_point_ops(positions, normals, reflectivities, light_position, light_color, camera_position, shininess,
+                        double_sided):
+    """`_specular_directional_ops` with the unit vector from the light's position to each point in place of the light
+    direction (`_diffuse_point_ops`' incident vector): operands [*, V, 3], light parameters [*, 3]."""
+    rel = positions - light_position[..., None, :]
+    incident = rel / (torch.linalg.norm(rel, dim=-1, keepdim=True) + 1.e-12)
+    reflected = incident + 2. * (normals * -incident).sum(-1, keepdim=True) * normals
+    to_camera = camera_position[..., None, :] - positions
+    cosines = ((to_camera / torch.linalg.norm(to_camera, dim=-1, keepdim=True) + 1.e-12) * reflected).sum(-1, keepdim=True)
+    cosines = cosines.abs() if double_sided else cosines.clamp_min(0.)
+    return light_color[..., None, :] * reflectivities * torch.pow(cosines, shininess)
+
+
+def _shade_lights_ops(positions, colors, normals, light_vectors, diffuse_colors, specular_colors, camera_position,
+                      shininess, ambient_color=None, point=None, double_sided=False):
+    """The framework-op statement of shade_lights: light arrays [N,3] or [B,N,3], camera [3] or [B,3]."""
+    dev, dt = positions.device, positions.dtype
+    as_t = lambda x: torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
+    bg = torch.isinf(positions).any(-1)
+    pos_d = _dilate_ops(positions, bg)
+    nrm_d = _dilate_ops(normals, bg)
+    valid = torch.isfinite(pos_d).all(-1, keepdim=True) & torch.isfinite(nrm_d).all(-1, keepdim=True)
+    frames = positions.shape[0] if positions.dim() == 4 else 1
+    pos_s, nrm_s, col_s = (torch.where(valid, x, 0.0).reshape(frames, -1, 3) for x in (pos_d, nrm_d, colors))
+    vectors, diffuse, specular, camera = (as_t(x) for x in (light_vectors, diffuse_colors, specular_colors,
+                                                            camera_position))
+    if isinstance(shininess, torch.Tensor):
+        shininess = as_t(shininess).reshape(())
+    # (the ambient term first, as `_shade_ops` forms it: autograd then adds the colour's three gradients in its order)
+    ambient = None if ambient_color is None else col_s * as_t(ambient_color)
+
+    def lit(pos, nrm, col, vectors, diffuse, specular, camera):
+        """the lights' sum over rows [R,3] under one set of lights [N,3] and one camera [3]"""
+        acc = None
+        for i in range(vectors.shape[0]):
+            if point is not None and point[i]:
+                d = _diffuse_point_ops(pos, nrm, col, vectors[i], diffuse[i], double_sided)
+                s = _specular_point_ops(pos, nrm, col, vectors[i], specular[i], camera, shininess, double_sided)
+            else:
+                d = _diffuse_directional_ops(nrm, col, vectors[i], diffuse[i], double_sided)
+                s = _specular_directional_ops(pos, nrm, col, vectors[i], specular[i], camera, shininess, double_sided)
+            acc = d + s if acc is None else acc + (d + s)
+        return torch.zeros_like(col) if acc is None else acc
+
+    if vectors.dim() == 3 or camera.dim() == 2:
+        per = lambda x, d, b: x[b] if x.dim() == d else x  # noqa: E731
+        acc = torch.stack([lit(pos_s[b], nrm_s[b], col_s[b], per(vectors, 3, b), per(diffuse, 3, b),
+                               per(specular, 3, b), per(camera, 2, b)) for b in range(frames)])
+    else:
+        acc = lit(pos_s.reshape(-1, 3), nrm_s.reshape(-1, 3), col_s.reshape(-1, 3), vectors, diffuse, specular,
+                  camera).reshape(col_s.shape)
+    if ambient is not None:
+        acc = acc + ambient
+    return acc.reshape(positions.shape), valid
+
+
+def _point_mask(point):
+    return sum(1 << i for i, on in enumerate(point or ()) if on)
+
+
+class _ShadeLightsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, positions, colors, normals, vectors, diffuse, specular, camera, ambient, shininess_t,
+                shininess, mask, double_sided):
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        pixels = torch.empty_like(positions)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        route = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        ctx.args = (vectors.shape[-2], mask, 1 if vectors.dim() == 3 else 0, 1 if camera.dim() == 2 else 0,
+                    shininess, double_sided)
+        n, mask, lights_pf, cam_pf, shininess, double_sided = ctx.args
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_deferred_shade_lights_fwd(
+                positions.data_ptr(), colors.data_ptr(), normals.data_ptr(), B, H, W, _ptr(ambient), n, mask,
+                lights_pf, vectors.data_ptr(), diffuse.data_ptr(), specular.data_ptr(), cam_pf, camera.data_ptr(),
+                shininess, _ptr(shininess_t), double_sided, pixels.data_ptr(), valid.data_ptr(), route.data_ptr(),
+                _stream(dev)))
+        ctx.save_for_backward(positions, colors, normals, vectors, diffuse, specular, camera, ambient, shininess_t,
+                              route)
+        valid = valid.view(torch.bool)  # (the kernel writes 0 / 1)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)  # (as the shade: no zero-filled "gradient" of valid)
+        return pixels, valid
+
+    @staticmethod
+    def backward(ctx, grad_pixels, _grad_valid):
+        _no_double_backward("shade_lights")
+        if grad_pixels is None:
+            return (None,) * 12
+        positions, colors, normals, vectors, diffuse, specular, camera, ambient, shininess_t, route = ctx.saved_tensors
+        n, mask, lights_pf, cam_pf, shininess, double_sided = ctx.args
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        grad_pixels = grad_pixels.contiguous()
+        # (NULL for the gradients nobody needs: the kernels then skip them, and with no parameter among them the
+        # partial sums and the second launch as well)
+        saved = (positions, colors, normals, vectors, diffuse, specular, camera, ambient, shininess_t)
+        grads = [torch.empty_like(t) if need and t is not None else None
+                 for t, need in zip(saved, ctx.needs_input_grad[:9])]
+        lib = _lib.load()
+        workspace, size = None, _lib._SZ(0)
+        if any(g is not None for g in grads[3:]):
+            _lib.check(lib.dirt_deferred_shade_lights_workspace(B, H, W, n, ctypes.byref(size)))
+            workspace = torch.empty((max(size.value, 4),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.dirt_deferred_shade_lights_bwd(
+                positions.data_ptr(), colors.data_ptr(), normals.data_ptr(), B, H, W, _ptr(ambient), n, mask,
+                lights_pf, vectors.data_ptr(), diffuse.data_ptr(), specular.data_ptr(), cam_pf, camera.data_ptr(),
+                shininess, _ptr(shininess_t), double_sided, grad_pixels.data_ptr(), route.data_ptr(),
+                _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[7]), _ptr(grads[3]), _ptr(grads[4]),
+                _ptr(grads[5]), _ptr(grads[6]), _ptr(grads[8]), _ptr(workspace), size.value, _stream(dev)))
+        return tuple(grads) + (None, None, None)
+
+
+def _lights_param(x, like, shapes):
+    """A light parameter usable by the fused kernels (a float32 tensor on like's device of one of `shapes`; it may
+    need a gradient), else None."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != like.device or \
+            tuple(x.shape) not in shapes:
+        return None
+    return x.contiguous()
+
+
+def shade_lights(positions, colors, normals, light_vectors, diffuse_colors, specular_colors, camera_position,
+                 shininess, ambient_color=None, point=None, double_sided=False):
+    """`shade` under N lights (0 <= N <= 8; N = 0 is ambient only), with gradients to the lights.
+
+    positions, colors, normals: the G-buffers, as for `shade`.  light_vectors, diffuse_colors, specular_colors: [N,3]
+    shared by the frames or [B,N,3] one set per frame, all three in the same form.  point: None (all directional) or
+    N Python bools; a directional light's row of light_vectors is its direction (used raw, as diffuse_directional
+    does), a point light's row is its position.  camera_position: [3] or [B,3].  shininess: a Python number, or a
+    one-element tensor (which can receive a gradient).  ambient_color: [3], or None for zero.
+
+    For a valid pixel, lights in index order: acc = (d_0 + s_0), acc = acc + (d_i + s_i), pixels = acc + colors *
+    ambient_color, with d_i, s_i = diffuse_directional, specular_directional for a directional light, and for a point
+    light diffuse_point and specular_directional with u = (p - light) / (|p - light| + 1e-12) as its direction (no
+    distance attenuation).  Dilation and (pixels, valid) are `shade`'s.
+
+    On the GPU (float32 tensors on one device) the forward is one fused launch and the backward two, whichever inputs
+    need gradients: the G-buffers, the light arrays, the camera, the ambient colour and a tensor shininess.  A
+    parameter's gradient is the sum of its per-pixel terms in a fixed order: bit-identical from run to run."""
+    fn = "shade_lights"
+    positions = torch.as_tensor(positions)
+    dev, dt = positions.device, positions.dtype
+    colors, normals = (torch.as_tensor(x, dtype=dt, device=dev) for x in (colors, normals))
+    if positions.dim() not in (3, 4) or positions.shape[-1] != 3 or colors.shape != positions.shape or \
+            normals.shape != positions.shape:
+        raise ValueError("%s: positions, colors, normals must share one shape [H, W, 3] or [B, H, W, 3]" % fn)
+    lights = [x if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=dt, device=dev)
+              for x in (light_vectors, diffuse_colors, specular_colors)]
+    if any(x.dim() not in (2, 3) or x.shape[-1] != 3 for x in lights):
+        raise ValueError("%s: light_vectors, diffuse_colors, specular_colors must be [N, 3] or [B, N, 3]" % fn)
+    if len({x.dim() for x in lights}) != 1:
+        raise ValueError("%s: the three light arrays must all be shared [N, 3] or all per frame [B, N, 3]" % fn)
+    if len({x.shape[-2] for x in lights}) != 1:
+        raise ValueError("%s: the three light arrays hold %s lights" % (fn, [x.shape[-2] for x in lights]))
+    n = lights[0].shape[-2]
+    if n > _lib.MAX_LIGHTS:
+        raise ValueError("%s: %d lights, at most %d" % (fn, n, _lib.MAX_LIGHTS))
+    frames = positions.shape[0] if positions.dim() == 4 else None
+    if lights[0].dim() == 3 and any(x.shape[0] != frames for x in lights):
+        raise ValueError("%s: per-frame light arrays need one set per frame of a [B, H, W, 3] batch" % fn)
+    if point is not None:
+        point = tuple(bool(b) for b in point)
+        if len(point) != n:
+            raise ValueError("%s: point has %d entries for %d lights" % (fn, len(point), n))
+    if not isinstance(camera_position, torch.Tensor):
+        camera_position = torch.as_tensor(camera_position, dtype=dt, device=dev)
+    if tuple(camera_position.shape) not in ((3,), (frames, 3)):
+        raise ValueError("%s: camera_position must be [3] or [B, 3]" % fn)
+    if isinstance(shininess, torch.Tensor) and shininess.numel() != 1:
+        raise ValueError("%s: shininess must be a number or a one-element tensor" % fn)
+    if _FUSED_ENABLED and _gpu_f32(positions, colors, normals) and \
+            (isinstance(shininess, (int, float)) or _gpu_f32(positions, shininess)):
+        light_shape = ((n, 3),) if lights[0].dim() == 2 else ((frames, n, 3),)
+        ps = [_lights_param(x, positions, light_shape) for x in lights]
+        ps.append(_lights_param(camera_position, positions, ((3,), (frames, 3))))
+        amb = None if ambient_color is None else _lights_param(ambient_color, positions, ((3,),))
+        if all(p is not None for p in ps) and (ambient_color is None or amb is not None):
+            ops = [x.contiguous() if x.dim() == 4 else x.contiguous()[None] for x in (positions, colors, normals)]
+            number = isinstance(shininess, (int, float))
+            pixels, valid = _ShadeLightsFn.apply(*ops, *ps, amb, None if number else shininess.contiguous(),
+                                                 float(shininess) if number else 0.0, _point_mask(point),
+                                                 1 if double_sided else 0)
+            return (pixels, valid) if positions.dim() == 4 else (pixels[0], valid[0])
+    return _shade_lights_ops(positions, colors, normals, lights[0], lights[1], lights[2], camera_position, shininess,
+                             ambient_color, point, double_sided)
 
 
 # ---- texture sampling

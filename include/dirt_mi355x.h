@@ -79,7 +79,8 @@ extern "C" {
  * dirt_rasterise_fwd_resolve; added at 13 without a bump, no signature or layout changed: dirt_dilate_fwd,
  * dirt_dilate_bwd, dirt_deferred_shade_fwd, dirt_deferred_shade_bwd, dirt_texture_sample_fwd,
  * dirt_texture_sample_bwd, dirt_texture_mip_layout, dirt_texture_mip_build_fwd, dirt_texture_mip_build_bwd,
- * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd) */
+ * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd, dirt_deferred_shade_lights_workspace,
+ * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -320,6 +321,46 @@ int dirt_deferred_shade_bwd(const float *positions, const float *colors, const f
                             const float *specular_color, const float *camera_position, float shininess,
                             int double_sided, const float *grad_pixels, const uint32_t *route, float *grad_positions,
                             float *grad_colors, float *grad_normals, void *stream);
+
+/* deferred_shade_lights: deferred_shade under n_lights lights (0..DIRT_MAX_LIGHTS; 0 = ambient only), with gradients
+ * to the light parameters.  Dilation, valid and the route word are deferred_shade's.  Bit i of point_mask makes light
+ * i a point light (bits at or above n_lights must be clear).  light_vectors, diffuse_colors, specular_colors are
+ * DEVICE arrays [n_lights,3] shared by the frames, or [B,n_lights,3] with lights_per_frame != 0; camera_position is
+ * [3], or [B,3] with camera_per_frame != 0; ambient_color is 3 floats shared by the frames, NULL = zero; the
+ * shininess is read from the device through shininess_ptr when that is not NULL, else it is shininess_value.  Nothing
+ * is copied from the host per call: the calls can be captured into a graph.  For a valid pixel, lights in index order:
+ *   acc = (d_0 + s_0);  acc = acc + (d_i + s_i);  pixels = acc + colors * ambient_color
+ *   directional light, row l (used raw): d = diffuse_directional, s = specular_directional, colours as reflectivities
+ *   point light, row = its position: u = (p - light) / (|p - light| + 1e-12); d = diffuse_point; s =
+ *   specular_directional with u in place of the direction (the gradient flows through u into p and the light's
+ *   position); no distance attenuation.
+ * Backward: grad_positions / grad_colors / grad_normals as deferred_shade_bwd's; grad_ambient [3], grad_light_vectors,
+ * grad_diffuse_colors, grad_specular_colors, grad_camera (shaped as their parameters) and grad_shininess [1] receive
+ * the sums of the per-pixel terms over the valid pixels of a frame (per-frame parameters) or of all frames (shared
+ * ones).  Each of the nine may be NULL; each requested one is fully overwritten.  With a parameter gradient
+ * requested, `workspace` must hold dirt_deferred_shade_lights_workspace() bytes (it needs no clearing): the first
+ * kernel stores per-chunk partial sums [B][chunks][7 + 9 n_lights] there -- one workgroup per 256 contiguous pixels
+ * of a frame, wave butterflies, then the four waves in order -- and a second kernel on the same stream adds the
+ * chunks of a frame and then the frames in fixed orders.  No float atomics: every gradient is bit-identical from run
+ * to run.  B == 0, or nothing requested, is DIRT_OK without a launch. */
+#define DIRT_MAX_LIGHTS 8
+int dirt_deferred_shade_lights_workspace(int B, int H, int W, int n_lights, size_t *bytes);
+int dirt_deferred_shade_lights_fwd(const float *positions, const float *colors, const float *normals, int B, int H,
+                                   int W, const float *ambient_color, int n_lights, unsigned point_mask,
+                                   int lights_per_frame, const float *light_vectors, const float *diffuse_colors,
+                                   const float *specular_colors, int camera_per_frame, const float *camera_position,
+                                   float shininess_value, const float *shininess_ptr, int double_sided, float *pixels,
+                                   uint8_t *valid, uint32_t *route, void *stream);
+int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, const float *normals, int B, int H,
+                                   int W, const float *ambient_color, int n_lights, unsigned point_mask,
+                                   int lights_per_frame, const float *light_vectors, const float *diffuse_colors,
+                                   const float *specular_colors, int camera_per_frame, const float *camera_position,
+                                   float shininess_value, const float *shininess_ptr, int double_sided,
+                                   const float *grad_pixels, const uint32_t *route, float *grad_positions,
+                                   float *grad_colors, float *grad_normals, float *grad_ambient,
+                                   float *grad_light_vectors, float *grad_diffuse_colors, float *grad_specular_colors,
+                                   float *grad_camera, float *grad_shininess, void *workspace, size_t workspace_bytes,
+                                   void *stream);
 
 /* Deferred texturing: bilinear sampling of a texture at a uv G-buffer, and its gradients.
  * texture [texture_frames,Th,Tw,C] (texture_frames = 1: shared by the B frames, = B: one per frame), uv [B,H,W,2],

@@ -1,0 +1,413 @@
+"""The fused shade_lights kernels (dirt_amd/csrc/shade_lights_kernels.h through dirt_amd.deferred.shade_lights) against
+the float64 statement of record (tests/shade_lights_cases.py).
+
+valid and the route word exact, invalid pixels exactly 0, valid pixels within the lighting contract per term and summed
+((1 + 2 N) * FWD_ATOL + FWD_RTOL * (|ambient| + sum |d_i| + sum |s_i|)); G-buffer gradients within GRAD_FRAC of their
+reference's scale (tests/lighting_cases.py::grad_ratio); parameter gradients within GRAD_FRAC of the sum of their
+absolute per-pixel terms (`absum`; tests/test_shade_lights_cpu.py holds the framework ops in float32 to half of that
+on the same cases), the 1x1 frames left out of that one check; every gradient bit-identical from run to run.  Each
+test prints its worst measured ratios of error to bound.
+"""
+import gc
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+import deferred_cases as dc
+import lighting_cases
+import shade_lights_cases as slc
+from dirt_amd import _lib, deferred
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+NAMES = ("positions", "colors", "normals")
+PARAMS = ("vectors", "diffuse", "specular", "camera", "ambient", "shininess")
+FRAC = lighting_cases.GRAD_FRAC
+
+
+def _gpu(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return t if dtype is None else t.to(dtype)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _node_names(y):
+    return [y.grad_fn.name()] + [fn.name() for fn, _ in y.grad_fn.next_functions if fn is not None]
+
+
+def _tensors(inputs, L, gbuf=(True, True, True), params=PARAMS, shininess="tensor", dtype=torch.float32):
+    """-> (the three G-buffers, {parameter name: tensor}), requiring gradients as asked"""
+    ts = [_gpu(a, dtype).requires_grad_(need) for a, need in zip(inputs, gbuf)]
+    ps = {"vectors": _gpu(L.vectors, dtype), "diffuse": _gpu(L.diffuse, dtype), "specular": _gpu(L.specular, dtype),
+          "camera": _gpu(L.camera, dtype)}
+    if L.ambient is not None:
+        ps["ambient"] = _gpu(L.ambient, dtype)
+    if shininess == "tensor":
+        ps["shininess"] = torch.tensor([float(L.shininess)], dtype=dtype, device=DEV)
+    for name, p in ps.items():
+        p.requires_grad_(name in params)
+    return ts, ps
+
+
+def _call(ts, ps, L, fn=None):
+    return (fn or deferred.shade_lights)(*ts, ps["vectors"], ps["diffuse"], ps["specular"], ps["camera"],
+                                         ps.get("shininess", L.shininess), ps.get("ambient"), L.point, L.double_sided)
+
+
+def _run(inputs, L, grad, gbuf=(True, True, True), params=PARAMS, shininess="tensor", dtype=torch.float32, fn=None):
+    """-> dict: pixels, valid (tensors), nodes (names around pixels' grad_fn), grads {name: numpy, or None where no
+    gradient was asked for}"""
+    ts, ps = _tensors(inputs, L, gbuf, params, shininess, dtype)
+    pixels, valid = _call(ts, ps, L, fn)
+    named = list(zip(NAMES, ts)) + list(ps.items())
+    wrt = [(n, t) for n, t in named if t.requires_grad]
+    grads = {n: None for n, _ in named}
+    if wrt:
+        got = torch.autograd.grad(pixels, [t for _, t in wrt], _gpu(grad, dtype), allow_unused=True)
+        for (n, t), g in zip(wrt, got):
+            grads[n] = (torch.zeros_like(t) if g is None else g).cpu().numpy()
+    torch.cuda.synchronize()
+    return {"pixels": pixels.detach(), "valid": valid, "nodes": _node_names(pixels) if wrt else [], "grads": grads}
+
+
+def _check(got, ref, n, tag, accuracy=True, names=NAMES + PARAMS):
+    """-> worst ratios (forward, G-buffer gradients, parameter gradients) of error to bound"""
+    pixels, valid = got["pixels"].cpu().numpy(), got["valid"].cpu().numpy()
+    assert valid.dtype == np.bool_ and valid.shape == ref["valid"].shape + (1,), tag
+    assert np.array_equal(valid[..., 0], ref["valid"]), tag
+    v = ref["valid"]
+    assert np.array_equal(pixels[~v], np.zeros_like(pixels[~v])), tag
+    err, bound = np.abs(pixels - ref["pixels"])[v], slc.fwd_bound(ref, n)[v]
+    fwd = float((err / bound).max()) if err.size else 0.0
+    assert fwd <= 1.0, (tag, fwd)
+    worst_g = worst_p = 0.0
+    for name in NAMES:
+        if name in names and got["grads"][name] is not None:
+            r = lighting_cases.grad_ratio(got["grads"][name], ref[name], "%s d %s" % (tag, name))
+            assert r <= 1.0, (tag, name, r)
+            worst_g = max(worst_g, r)
+    for name, want in ref["params"].items():
+        g = got["grads"].get(name)
+        if name not in names or g is None or np.size(want) == 0:
+            continue
+        assert np.all(np.isfinite(g)), (tag, name)
+        if accuracy:
+            r = slc.param_ratio(g, want, ref["absum"][name], FRAC)
+            assert r <= 1.0, (tag, name, r)
+            worst_p = max(worst_p, r)
+    print("shade_lights %s: forward %.3f of its bound, G-buffer gradients %.3f, parameter gradients %.3f of theirs"
+          % (tag, fwd, worst_g, worst_p))
+    return fwd, worst_g, worst_p
+
+
+def _same_grads(a, b, tag):
+    for name in a["grads"]:
+        if a["grads"][name] is None or b["grads"].get(name) is None:
+            continue
+        assert np.array_equal(_bits(a["grads"][name]), _bits(b["grads"][name])), (tag, name)
+
+
+def _raw_route(inputs, L):
+    """dirt_deferred_shade_lights_fwd itself: the route word as numpy uint32"""
+    ts, ps = _tensors(inputs, L, (False,) * 3, (), "number")
+    B, H, W, _ = ts[0].shape
+    pixels = torch.empty_like(ts[0])
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=DEV)
+    route = torch.empty((B, H, W), dtype=torch.int32, device=DEV)
+    amb = ps.get("ambient")
+    _lib.check(_lib.load().dirt_deferred_shade_lights_fwd(
+        ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), B, H, W, None if amb is None else amb.data_ptr(), L.n,
+        sum(1 << i for i, on in enumerate(L.point) if on), int(L.vectors.ndim == 3), ps["vectors"].data_ptr(),
+        ps["diffuse"].data_ptr(), ps["specular"].data_ptr(), int(L.camera.ndim == 2), ps["camera"].data_ptr(),
+        float(L.shininess), None, int(L.double_sided), pixels.data_ptr(), valid.data_ptr(), route.data_ptr(),
+        torch.cuda.current_stream(DEV).cuda_stream))
+    torch.cuda.synchronize()
+    return route.cpu().numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("ident", dc.FRAME_IDS)
+def test_matches_the_statement(ident):
+    """One directional and one point light over the table of edge frames, every gradient requested."""
+    inputs, L, grad, ref = slc.case(ident)
+    got = _run(inputs, L, grad)
+    assert any("_ShadeLightsFn" in n for n in got["nodes"]), got["nodes"]
+    assert not got["valid"].requires_grad
+    assert np.array_equal(_raw_route(inputs, L), ref["route"]), ident
+    _check(got, ref, L.n, ident, accuracy=ident in slc.accuracy_frames())
+    _same_grads(got, _run(inputs, L, grad), ident)  # bit-identical from run to run
+    if ident.endswith("all_background"):
+        for name, g in got["grads"].items():
+            assert not np.any(g), (ident, name)  # exactly 0
+
+
+def _edge_case(H, W, B=1, valid_count=None, seed=0, **lights):
+    """A fully covered frame (valid_count: only its first pixels have a usable normal) and its statement"""
+    rng = np.random.default_rng([seed, H, W, B, valid_count or 0])
+    covered = np.ones((B, H, W), bool)
+    invalid = None
+    if valid_count is not None:
+        invalid = (np.arange(H * W) >= valid_count).reshape(1, H, W).repeat(B, 0)
+    inputs = slc.random_input(rng, covered, invalid)
+    L = slc.draw_lights(rng, B, **lights)
+    grad = rng.standard_normal(inputs[0].shape).astype(np.float32)
+    return inputs, L, grad
+
+
+CHUNK = 256  # kSlChunk: the pixels one workgroup of the backward's first kernel owns
+
+
+@pytest.mark.parametrize("count", sorted({63, 64, 65, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 1023, 1024, 1025}))
+def test_reduction_edges(count):
+    """Frames of `count` pixels, and `count` valid pixels in a larger frame: a wave, a workgroup (which is a chunk) and four chunks, each one
+    pixel short, full, and one over."""
+    for H, W, valid_count in ((1, count, None), (3, 700, count)):
+        inputs, L, grad = _edge_case(H, W, valid_count=valid_count)
+        ref = slc.shade_lights(*inputs, L, grad)
+        assert int(ref["valid"].sum()) == count
+        got = _run(inputs, L, grad)
+        _check(got, ref, L.n, "%dx%d with %d valid" % (H, W, count))
+        _same_grads(got, _run(inputs, L, grad), count)
+
+
+def test_two_frames_of_several_ragged_chunks():
+    """33 x 65 = 2145 pixels: nine chunks a frame, the last one ragged, in each of two frames with their own lights"""
+    rng = np.random.default_rng(33)
+    covered = rng.random((2, 33, 65)) < 0.7
+    inputs = slc.random_input(rng, covered)
+    grad = rng.standard_normal(inputs[0].shape).astype(np.float32)
+    for per_frame in (False, True):
+        L = slc.draw_lights(rng, 2, 3, "mixed", per_frame)
+        ref = slc.shade_lights(*inputs, L, grad)
+        got = _run(inputs, L, grad)
+        _check(got, ref, L.n, "2x33x65 per_frame=%d" % per_frame)
+        _same_grads(got, _run(inputs, L, grad), per_frame)
+
+
+def test_more_chunks_than_the_second_kernel_has_threads():
+    """512 x 513: 1026 chunks, four times the reducing workgroup's 256 threads and two over.  Against `_shade_lights_ops` in
+    float64 on the GPU; absum (the parameter bound's scale) from the statement, which is plain numpy here: the frame
+    has one background row only."""
+    rng = np.random.default_rng(512)
+    covered = np.ones((1, 512, 513), bool)
+    covered[0, 300] = False
+    inputs = slc.random_input(rng, covered)
+    L = slc.draw_lights(rng, 1, 2, "mixed")
+    grad = rng.standard_normal(inputs[0].shape).astype(np.float32)
+    got = _run(inputs, L, grad)
+    assert any("_ShadeLightsFn" in n for n in got["nodes"])
+    want = _run(inputs, L, grad, dtype=torch.float64, fn=deferred._shade_lights_ops)
+    stmt = slc.shade_lights(*inputs, L, grad)
+    ref = dict(stmt, pixels=want["pixels"].cpu().numpy(), params={k: want["grads"][k].reshape(np.shape(v))
+                                                                   for k, v in stmt["params"].items()})
+    for name in NAMES:
+        ref[name] = want["grads"][name]
+    assert np.array_equal(want["valid"].cpu().numpy()[..., 0], stmt["valid"])
+    _check(got, ref, L.n, "512x513")
+    _same_grads(got, _run(inputs, L, grad), "512x513")
+
+
+def test_per_frame_lights_do_not_leak_across_frames():
+    """3x5x6-leak with one set of lights and one camera per frame: the all-background outer frames' parameter gradients
+    are exactly 0, the middle frame's match the statement."""
+    inputs, L, grad, ref = slc.case("3x5x6-leak", 2, "mixed", True)
+    got = _run(inputs, L, grad)
+    _check(got, ref, L.n, "leak, per frame")
+    for name in ("vectors", "diffuse", "specular", "camera"):
+        g = got["grads"][name]
+        assert g.shape[0] == 3 and not np.any(g[[0, 2]]) and np.any(g[1]), name
+    _same_grads(got, _run(inputs, L, grad), "leak")
+
+
+@pytest.mark.parametrize("kinds", ["directional", "point", "mixed"])
+@pytest.mark.parametrize("n", [0, 1, 8])
+def test_light_counts_and_kinds(n, kinds):
+    inputs, L, grad, ref = slc.case("15x17-checkerboard", n, kinds)
+    got = _run(inputs, L, grad)
+    assert any("_ShadeLightsFn" in x for x in got["nodes"])
+    _check(got, ref, n, "N=%d %s" % (n, kinds))
+    if n == 0:
+        assert not np.any(got["grads"]["camera"]) and not np.any(got["grads"]["shininess"])
+        assert got["grads"]["vectors"].shape == (0, 3)
+
+
+@pytest.mark.parametrize("two", [False, True], ids=["one_sided", "double_sided"])
+@pytest.mark.parametrize("shininess", [0, 1, 2.5, 6, 50])
+def test_shininess_and_clamps(shininess, two):
+    """The exponent as a one-element tensor (with its gradient) and as a Python number: the same bits."""
+    inputs, L, grad, ref = slc.case("63x65-hole", 2, "mixed", False, shininess, two)
+    as_tensor = _run(inputs, L, grad)
+    _check(as_tensor, ref, L.n, "k=%g two=%d (tensor)" % (shininess, two))
+    as_number = _run(inputs, L, grad, shininess="number")
+    assert any("_ShadeLightsFn" in x for x in as_number["nodes"])
+    assert torch.equal(as_tensor["pixels"], as_number["pixels"])
+    assert as_number["grads"].get("shininess") is None
+    _same_grads(as_tensor, as_number, shininess)
+
+
+def test_gradient_subsets():
+    """Every subset of the G-buffers with all and with no parameter, every subset of the parameters with all the
+    G-buffers: the requested gradients are bit-identical to the all-requested run's, the others None; the G-buffer
+    gradients do not depend on whether a parameter is requested (one kernel with the sums, one without)."""
+    inputs, L, grad, ref = slc.case("15x17-block_br")
+    full = _run(inputs, L, grad)
+    _check(full, ref, L.n, "all gradients")
+    subsets = [(g, p) for g in itertools.product((False, True), repeat=3) for p in ((), PARAMS)]
+    subsets += [((True,) * 3, tuple(n for n, on in zip(PARAMS, pick) if on))
+                for pick in itertools.product((False, True), repeat=len(PARAMS))]
+    for gbuf, params in subsets:
+        got = _run(inputs, L, grad, gbuf, params)
+        assert torch.equal(got["pixels"], full["pixels"])
+        for name, need in list(zip(NAMES, gbuf)) + [(n, n in params) for n in PARAMS]:
+            assert (got["grads"][name] is not None) == need, (gbuf, params, name)
+        _same_grads(got, full, (gbuf, params))
+        if any(gbuf) or params:
+            assert any("_ShadeLightsFn" in x for x in got["nodes"])
+
+
+def test_nan_normal_invalidates_only_its_reach():
+    """A NaN normal at a covered pixel on the silhouette: that pixel and the background neighbours whose window holds
+    it are invalid; every output and gradient, the parameters' included, stays finite and as the statement's."""
+    ident = "15x17-block_tl"  # covered rows 0..7, columns 0..8
+    clean, L, grad, _ = slc.case(ident)
+    pos, col, nrm = (a.copy() for a in clean)
+    nrm[0, 7, 8, 1] = np.nan
+    ref = slc.shade_lights(pos, col, nrm, L, grad)
+    for y, x0 in ((7, 8), (8, 7), (8, 8), (8, 9), (7, 9), (6, 9)):
+        assert not ref["valid"][0, y, x0]
+    assert ref["valid"][0, 6, 8] and ref["valid"][0, 5, 9]
+    got = _run((pos, col, nrm), L, grad)
+    _check(got, ref, L.n, "nan normal")
+    assert all(np.all(np.isfinite(g)) for g in got["grads"].values()) and bool(torch.isfinite(got["pixels"]).all())
+
+
+def test_one_directional_light_against_shade():
+    """N = 1 directional against deferred.shade on the same G-buffers: valid equal, pixels and G-buffer gradients each
+    within the statement's bounds (the two kernels may contract their arithmetic differently: bit-equality is
+    printed, not required)."""
+    inputs, L0, ref0, grad, vjp0 = dc.shade_case("63x65-checkerboard")
+    L = slc.LightSet(L0.direction[None], L0.diffuse[None], L0.specular[None], L0.camera, L0.ambient, L0.shininess,
+                     (False,), L0.double_sided)
+    got = _run(inputs, L, grad, params=(), shininess="number")
+    ts = [_gpu(a).requires_grad_(True) for a in inputs]
+    pixels, valid = deferred.shade(*ts, *[_gpu(v) for v in L0.vectors()], L0.shininess, L0.double_sided)
+    grads = torch.autograd.grad(pixels, ts, _gpu(grad))
+    assert torch.equal(valid, got["valid"])
+    ref = slc.shade_lights(*inputs, L, grad)
+    _check(got, ref, 1, "N=1 directional")
+    assert np.abs(ref["pixels"] - ref0["pixels"]).max() <= 1e-12
+    equal = torch.equal(pixels.detach(), got["pixels"])
+    for name, g in zip(NAMES, grads):
+        r = lighting_cases.grad_ratio(g.cpu().numpy(), ref[name], name)
+        assert r <= 1.0, (name, r)
+        equal = equal and np.array_equal(_bits(g.cpu().numpy()), _bits(got["grads"][name]))
+    v = ref["valid"]
+    assert np.all(np.abs(pixels.detach().cpu().numpy() - ref["pixels"])[v] <= slc.fwd_bound(ref, 1)[v])
+    print("N = 1 directional against deferred.shade: bit-equal pixels and G-buffer gradients: %s" % equal)
+
+
+def test_forms(monkeypatch):
+    """[H,W,3] and non-contiguous inputs run the fused kernels and give the batched, contiguous result; float64,
+    DIRT_FUSED_DEFERRED=0 and CPU tensors take the statement."""
+    inputs, L, grad, ref = slc.case("15x17-island")
+    base = _run(inputs, L, grad)
+    one = _run([a[0] for a in inputs], L, grad[0])
+    assert one["pixels"].shape == (15, 17, 3) and one["valid"].shape == (15, 17, 1)
+    assert any("_ShadeLightsFn" in x for x in one["nodes"])
+    assert torch.equal(one["pixels"], base["pixels"][0])
+    for name in base["grads"]:
+        assert np.array_equal(_bits(one["grads"][name]).reshape(-1), _bits(base["grads"][name]).reshape(-1)), name
+    wide = [torch.zeros((1, 15, 17, 6), device=DEV) for _ in inputs]
+    for w, a in zip(wide, inputs):
+        w[..., ::2] = _gpu(a)
+    ts, ps = _tensors(inputs, L)
+    wide_lights = torch.zeros((2, 6), device=DEV)
+    wide_lights[:, ::2] = ps["vectors"].detach()
+    wl = wide_lights.requires_grad_(True)
+    ws = [w.requires_grad_(True) for w in wide]
+    pixels, valid = _call([w[..., ::2] for w in ws], dict(ps, vectors=wl[:, ::2]), L)
+    assert any("_ShadeLightsFn" in x for x in _node_names(pixels))
+    pixels.backward(_gpu(grad))
+    assert torch.equal(pixels.detach(), base["pixels"]) and torch.equal(valid, base["valid"])
+    for w, name in zip(ws, NAMES):
+        assert np.array_equal(_bits(w.grad.cpu().numpy()[..., ::2]), _bits(base["grads"][name])), name
+    assert np.array_equal(_bits(wl.grad.cpu().numpy()[:, ::2]), _bits(base["grads"]["vectors"]))
+
+    def statement(got, tol_fwd):
+        assert not any("_ShadeLightsFn" in x for x in got["nodes"]), got["nodes"]
+        assert np.array_equal(got["valid"].cpu().numpy()[..., 0], ref["valid"])
+        assert np.all(np.abs(got["pixels"].cpu().numpy() - ref["pixels"]) <= tol_fwd)
+
+    f64 = _run(inputs, L, grad, dtype=torch.float64)
+    statement(f64, 1e-12)
+    for name, want in ref["params"].items():
+        assert np.abs(f64["grads"][name].reshape(np.shape(want)) - want).max() <= 1e-12 * max(1, np.abs(want).max())
+    cpu = deferred.shade_lights(*[torch.from_numpy(a) for a in inputs], *[torch.from_numpy(x).requires_grad_(True)
+                                for x in (L.vectors, L.diffuse, L.specular, L.camera)], L.shininess,
+                                torch.from_numpy(L.ambient), L.point)
+    assert "_ShadeLightsFn" not in cpu[0].grad_fn.name() and cpu[0].device.type == "cpu"
+    monkeypatch.setattr(deferred, "_FUSED_ENABLED", False)
+    statement(_run(inputs, L, grad), slc.fwd_bound(ref, L.n))
+
+
+def test_double_backward_raises_on_the_fused_path_and_works_on_the_statement(monkeypatch):
+    inputs, L, grad, ref = slc.case("15x17-hole")
+    ts, ps = _tensors(inputs, L)
+    pixels, _ = _call(ts, ps, L)
+    with pytest.raises(RuntimeError, match="create_graph"):
+        torch.autograd.grad(pixels.square().sum(), [ps["vectors"]], create_graph=True)
+    monkeypatch.setattr(deferred, "_FUSED_ENABLED", False)
+    pixels, _ = _call(ts, ps, L)
+    gv, = torch.autograd.grad(pixels.square().sum(), [ps["vectors"]], create_graph=True)
+    gg, = torch.autograd.grad(gv.sum(), [ts[2]])
+    assert bool(torch.isfinite(gg).all()) and float(gg.abs().max()) > 0
+
+
+def test_captures_into_a_graph():
+    """One forward and backward with every parameter gradient captured with torch.cuda.graph, replayed after the
+    G-buffers and the lights changed in place: equal to the eager result bit for bit."""
+    first, L1, grad, _ = slc.case("63x65-block_tl")
+    second, L2 = slc.case("63x65-checkerboard")[0], slc.light_set("63x65-checkerboard")
+    ts, ps = _tensors(first, L1)
+    g = _gpu(grad)
+    named = list(zip(NAMES, ts)) + list(ps.items())
+    out = {}
+
+    def step():
+        pixels, valid = _call(ts, ps, L1)
+        out["pixels"], out["valid"] = pixels, valid
+        out["grads"] = torch.autograd.grad(pixels, [t for _, t in named], g)
+
+    gc.collect()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    out.clear()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    with torch.no_grad():
+        for t, a in zip(ts, second):
+            t.copy_(_gpu(a))
+        for name in ("vectors", "diffuse", "specular", "camera", "ambient"):
+            ps[name].copy_(_gpu(getattr(L2, name)))
+        ps["shininess"].fill_(2.5)
+    graph.replay()
+    torch.cuda.synchronize()
+    got = (out["pixels"].detach().clone(), out["valid"].clone(), [x.clone() for x in out["grads"]])
+    del graph
+    out.clear()
+    L2.shininess = 2.5
+    eager = _run(second, L2, grad)
+    assert L1.point == L2.point
+    assert torch.equal(got[0], eager["pixels"]) and torch.equal(got[1], eager["valid"])
+    for (name, _), a in zip(named, got[2]):
+        assert np.array_equal(_bits(a.cpu().numpy()), _bits(eager["grads"][name])), name
