@@ -1,5 +1,9 @@
 // Part of dirt_raster.hip's translation unit: included inside its anonymous namespace after lighting_kernels.h
-// (ld3 / st3 / dot3 ..., shade_clamp, shade_clamp_grad, spec_terms, light_blocks).  Not a standalone header.
+// (ld3 / st3 / dot3 ..., shade_clamp, shade_clamp_grad, spec_terms, light_blocks).  Not a standalone header.  What the
+// shade shares with shade_lights_kernels.h lives here: the route word's accessors (route_code, route_normal_code,
+// route_normals), pixel_at, window_max, routed3 and ShadeAdjoint.  The forwards' opening, the backwards' six-sum gather
+// and the diffuse and specular adjoints stay written out in each kernel: as shared functions they moved the listings
+// of kernels that then measured slower, or raised a register count.
 //
 // The pixel-space stage of deferred shading (the reference's samples/deferred.py:85-115, as
 // tests/deferred_pipeline.py::shade states it with selects): silhouette dilation of the G-buffers by a 3x3 max where
@@ -22,6 +26,12 @@
 
 constexpr uint32_t kRouteOwn = 15u;
 constexpr uint32_t kRouteValid = 0x80000000u;
+constexpr int kRouteNormals = 12;  // the shade's route word: first bit of the normals' codes
+// code c of a packed word (of the shade's word: position code c); normal code c of the shade's word; its normals' codes
+// as a packed word of their own
+__device__ __forceinline__ uint32_t route_code(uint32_t codes, int c) { return (codes >> (4 * c)) & 15u; }
+__device__ __forceinline__ uint32_t route_normal_code(uint32_t r, int c) { return (r >> (kRouteNormals + 4 * c)) & 15u; }
+__device__ __forceinline__ uint32_t route_normals(uint32_t r) { return r >> kRouteNormals; }
 
 struct PixelAt {
     int64_t f0;  // first pixel of the frame
@@ -85,7 +95,7 @@ __device__ __forceinline__ uint32_t route_own()
 __device__ __forceinline__ bool route_any(uint32_t codes, int n, uint32_t want)
 {
     bool hit = false;
-    for (int c = 0; c < n; ++c) hit = hit || ((codes >> (4 * c)) & 15u) == want;
+    for (int c = 0; c < n; ++c) hit = hit || route_code(codes, c) == want;
     return hit;
 }
 
@@ -125,7 +135,7 @@ __global__ __launch_bounds__(kLightThreads) void dilate_bwd_kernel(const float *
     const uint32_t r = route[p];
     float acc[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = ((r >> (4 * c)) & 15u) == kRouteOwn ? grad[p * C + c] : 0.0f;
+    for (int c = 0; c < C; ++c) acc[c] = route_code(r, c) == kRouteOwn ? grad[p * C + c] : 0.0f;
 #pragma unroll
     for (int dy = -1; dy <= 1; ++dy) {
         const int yy = at.y + dy;
@@ -140,7 +150,7 @@ __global__ __launch_bounds__(kLightThreads) void dilate_bwd_kernel(const float *
             const uint32_t rq = route[q];
 #pragma unroll
             for (int c = 0; c < C; ++c)
-                if (((rq >> (4 * c)) & 15u) == back) acc[c] += grad[q * C + c];
+                if (route_code(rq, c) == back) acc[c] += grad[q * C + c];
         }
     }
 #pragma unroll
@@ -162,7 +172,7 @@ __device__ __forceinline__ float3 routed3(const float *__restrict__ x, PixelAt a
     float v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const uint32_t k = (codes >> (4 * c)) & 15u;
+        const uint32_t k = route_code(codes, c);
         int yy = at.y, xx = at.x;
         if (k <= 8u) {
             const int ky = (int)(k / 3u);
@@ -194,7 +204,7 @@ __global__ __launch_bounds__(kLightThreads) void deferred_shade_fwd_kernel(
         const PixelAt at = pixel_at(p, H, W);
         float mp[3] = {0.0f, 0.0f, 0.0f}, mn[3] = {0.0f, 0.0f, 0.0f};
         r = window_max<3>(positions, at, H, W, mp);
-        r |= window_max<3>(normals, at, H, W, mn) << 12;
+        r |= window_max<3>(normals, at, H, W, mn) << kRouteNormals;
         pos = make_float3(mp[0], mp[1], mp[2]);
         nv = make_float3(mn[0], mn[1], mn[2]);
     }
@@ -264,15 +274,15 @@ __global__ __launch_bounds__(kLightThreads) void deferred_shade_bwd_kernel(
     ShadeAdjoint own;
     own.pos = own.nrm = own.col = zero;
     if (r & kRouteValid)
-        own = shade_adjoint(routed3(positions, at, H, W, r), routed3(normals, at, H, W, r >> 12), ld3(colors + p * 3),
-                            ld3(grad + p * 3), L);
+        own = shade_adjoint(routed3(positions, at, H, W, r), routed3(normals, at, H, W, route_normals(r)),
+                            ld3(colors + p * 3), ld3(grad + p * 3), L);
     if (grad_colors) st3(grad_colors + p * 3, own.col);
     if (!grad_positions && !grad_normals) return;
     float acc[6];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        acc[c] = ((r >> (4 * c)) & 15u) == kRouteOwn ? (&own.pos.x)[c] : 0.0f;
-        acc[3 + c] = ((r >> (12 + 4 * c)) & 15u) == kRouteOwn ? (&own.nrm.x)[c] : 0.0f;
+        acc[c] = route_code(r, c) == kRouteOwn ? (&own.pos.x)[c] : 0.0f;
+        acc[3 + c] = route_normal_code(r, c) == kRouteOwn ? (&own.nrm.x)[c] : 0.0f;
     }
 #pragma unroll
     for (int dy = -1; dy <= 1; ++dy) {
@@ -292,12 +302,12 @@ __global__ __launch_bounds__(kLightThreads) void deferred_shade_bwd_kernel(
             if (!(rq & kRouteValid) || !route_any(rq, 6, back)) continue;
             const ShadeAdjoint a =
                 self ? own
-                     : shade_adjoint(routed3(positions, aq, H, W, rq), routed3(normals, aq, H, W, rq >> 12),
+                     : shade_adjoint(routed3(positions, aq, H, W, rq), routed3(normals, aq, H, W, route_normals(rq)),
                                      ld3(colors + q * 3), ld3(grad + q * 3), L);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                if (((rq >> (4 * c)) & 15u) == back) acc[c] += (&a.pos.x)[c];
-                if (((rq >> (12 + 4 * c)) & 15u) == back) acc[3 + c] += (&a.nrm.x)[c];
+                if (route_code(rq, c) == back) acc[c] += (&a.pos.x)[c];
+                if (route_normal_code(rq, c) == back) acc[3 + c] += (&a.nrm.x)[c];
             }
         }
     }

@@ -1468,6 +1468,12 @@ void launch_dilate_bwd(const float *grad, const uint32_t *route, int H, int W, i
     dilate_bwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(grad, route, H, W, n, grad_x);
 }
 
+ShadeLights shade_lights_of(const float *ambient_color, const float *light_direction, const float *diffuse_color,
+                            const float *specular_color, const float *camera_position, float shininess, int double_sided)
+{
+    return {ambient_color, light_direction, diffuse_color, specular_color, camera_position, shininess, double_sided};
+}
+
 }  // namespace
 
 extern "C" {
@@ -1514,8 +1520,8 @@ int dirt_deferred_shade_fwd(const float *positions, const float *colors, const f
         !camera_position || !pixels || !valid || !route)
         return fail(DIRT_EINVAL, "deferred_shade: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const ShadeLights L = {ambient_color, light_direction, diffuse_color, specular_color, camera_position, shininess,
-                           double_sided};
+    const ShadeLights L = shade_lights_of(ambient_color, light_direction, diffuse_color, specular_color,
+                                          camera_position, shininess, double_sided);
     deferred_shade_fwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
         positions, colors, normals, H, W, n, L, pixels, valid, route);
     HIP_TRY(hipGetLastError());
@@ -1535,8 +1541,8 @@ int dirt_deferred_shade_bwd(const float *positions, const float *colors, const f
         !camera_position || !grad_pixels || !route)
         return fail(DIRT_EINVAL, "deferred_shade: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const ShadeLights L = {ambient_color, light_direction, diffuse_color, specular_color, camera_position, shininess,
-                           double_sided};
+    const ShadeLights L = shade_lights_of(ambient_color, light_direction, diffuse_color, specular_color,
+                                          camera_position, shininess, double_sided);
     deferred_shade_bwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
         positions, colors, normals, H, W, n, L, grad_pixels, route, grad_positions, grad_colors, grad_normals);
     HIP_TRY(hipGetLastError());
@@ -1561,6 +1567,15 @@ int shade_lights_sizes(int B, int H, int W, int n_lights, unsigned point_mask, i
     }
     if (point_mask >> n_lights) return fail(DIRT_EINVAL, "deferred_shade_lights: point_mask has bits past the lights");
     return DIRT_OK;
+}
+
+ShadeLightsArgs shade_lights_args(const float *ambient_color, int n_lights, unsigned point_mask, int lights_per_frame,
+                                  const float *light_vectors, const float *diffuse_colors,
+                                  const float *specular_colors, int camera_per_frame, const float *camera_position,
+                                  float shininess_value, const float *shininess_ptr, int double_sided)
+{
+    return {ambient_color, light_vectors, diffuse_colors, specular_colors, camera_position, shininess_ptr,
+            shininess_value, n_lights, point_mask, lights_per_frame != 0, camera_per_frame != 0, double_sided};
 }
 
 int64_t shade_lights_chunks(int H, int W) { return ((int64_t)H * W + kSlChunk - 1) / kSlChunk; }
@@ -1599,9 +1614,9 @@ int dirt_deferred_shade_lights_fwd(const float *positions, const float *colors, 
         (n_lights > 0 && (!light_vectors || !diffuse_colors || !specular_colors || !camera_position)))
         return fail(DIRT_EINVAL, "deferred_shade_lights: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const ShadeLightsArgs A = {ambient_color, light_vectors, diffuse_colors, specular_colors, camera_position,
-                               shininess_ptr, shininess_value, n_lights, point_mask, lights_per_frame != 0,
-                               camera_per_frame != 0, double_sided};
+    const ShadeLightsArgs A = shade_lights_args(ambient_color, n_lights, point_mask, lights_per_frame, light_vectors,
+                                                diffuse_colors, specular_colors, camera_per_frame, camera_position,
+                                                shininess_value, shininess_ptr, double_sided);
     shade_lights_fwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
         positions, colors, normals, H, W, n, A, pixels, valid, route);
     HIP_TRY(hipGetLastError());
@@ -1633,9 +1648,9 @@ int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, 
         return fail(DIRT_EINVAL, "deferred_shade_lights: workspace smaller than "
                                  "dirt_deferred_shade_lights_workspace() reports");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const ShadeLightsArgs A = {ambient_color, light_vectors, diffuse_colors, specular_colors, camera_position,
-                               shininess_ptr, shininess_value, n_lights, point_mask, lights_per_frame != 0,
-                               camera_per_frame != 0, double_sided};
+    const ShadeLightsArgs A = shade_lights_args(ambient_color, n_lights, point_mask, lights_per_frame, light_vectors,
+                                                diffuse_colors, specular_colors, camera_per_frame, camera_position,
+                                                shininess_value, shininess_ptr, double_sided);
     const int chunks = (int)shade_lights_chunks(H, W);  // (at most 8192^2 / 1024)
     const dim3 grid((unsigned)chunks, (unsigned)std::min(B, 65535));
     float *partial = static_cast<float *>(workspace);
@@ -1664,23 +1679,47 @@ int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, 
 
 namespace {
 
-// the argument checks of the two entry points beyond deferred_sizes'
-int texture_sizes(int texture_frames, int Th, int Tw, int B, int H, int W, int C, int wrap, int64_t *pixels)
+struct SampleGrid {
+    int64_t pixels;        // B * H * W (0: nothing to do)
+    int tiles_x, tiles_y;  // the backward's kTexTile x kTexTile screen tiles over one frame
+};
+
+int texture_dims(const char *op, int Th, int Tw)
 {
-    const int rc = deferred_sizes("texture_sample", B, H, W, C, pixels);
-    if (rc) return rc;
-    *pixels = 0;
-    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM)
-        return fail(DIRT_EINVAL, "texture_sample: texture height, width must be in 1..8192");
-    if (wrap != DIRT_TEXTURE_CLAMP && wrap != DIRT_TEXTURE_REPEAT)
-        return fail(DIRT_EINVAL, "texture_sample: wrap must be DIRT_TEXTURE_CLAMP or DIRT_TEXTURE_REPEAT");
-    if (B > 0 && texture_frames != 1 && texture_frames != B)
-        return fail(DIRT_EINVAL, "texture_sample: texture_frames must be 1 or the batch size");
-    const int64_t tiles = (int64_t)((H + kTexTile - 1) / kTexTile) * ((W + kTexTile - 1) / kTexTile);
-    if ((int64_t)B * tiles > 0x7fffffffLL)
-        return fail(DIRT_EINVAL, "texture_sample: too large (more screen tiles than one launch covers)");
-    *pixels = (int64_t)B * H * W;
+    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: texture height, width must be in 1..%d", op, DIRT_MAX_DIM);
+        return fail(DIRT_EINVAL, msg);
+    }
     return DIRT_OK;
+}
+
+// the argument checks that the plain and the mip sample entry points share beyond deferred_sizes' and the texture's
+// own: the wrap, the texture's frames against the batch, the tiles of one launch; DIRT_OK with g's tile grid
+int sample_sizes(const char *op, int texture_frames, int B, int H, int W, int wrap, SampleGrid *g)
+{
+    const auto bad = [op](const char *what) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: %s", op, what);
+        return fail(DIRT_EINVAL, msg);
+    };
+    if (wrap != DIRT_TEXTURE_CLAMP && wrap != DIRT_TEXTURE_REPEAT)
+        return bad("wrap must be DIRT_TEXTURE_CLAMP or DIRT_TEXTURE_REPEAT");
+    if (B > 0 && texture_frames != 1 && texture_frames != B) return bad("texture_frames must be 1 or the batch size");
+    g->tiles_x = (W + kTexTile - 1) / kTexTile;
+    g->tiles_y = (H + kTexTile - 1) / kTexTile;
+    if ((int64_t)B * g->tiles_y * g->tiles_x > 0x7fffffffLL)
+        return bad("too large (more screen tiles than one launch covers)");
+    return DIRT_OK;
+}
+
+int texture_sizes(int texture_frames, int Th, int Tw, int B, int H, int W, int C, int wrap, SampleGrid *g)
+{
+    int rc = deferred_sizes("texture_sample", B, H, W, C, &g->pixels);
+    if (!rc) rc = texture_dims("texture_sample", Th, Tw);
+    if (!rc) rc = sample_sizes("texture_sample", texture_frames, B, H, W, wrap, g);
+    if (rc) g->pixels = 0;
+    return rc;
 }
 
 template <int C>
@@ -1694,12 +1733,12 @@ void launch_texture_fwd(const float *texture, int64_t frame_stride, int Th, int 
 
 template <int C>
 void launch_texture_bwd(const float *texture, int64_t frame_stride, int Th, int Tw, const float *uv,
-                        const uint8_t *mask, int B, int H, int W, int wrap, const float *grad, float *grad_texture,
-                        float *grad_uv, hipStream_t stream)
+                        const uint8_t *mask, int B, int H, int W, SampleGrid g, int wrap, const float *grad,
+                        float *grad_texture, float *grad_uv, hipStream_t stream)
 {
-    const int tiles_x = (W + kTexTile - 1) / kTexTile, tiles_y = (H + kTexTile - 1) / kTexTile;
-    texture_sample_bwd_kernel<C><<<dim3((unsigned)((int64_t)B * tiles_y * tiles_x)), dim3(kLightThreads), 0, stream>>>(
-        texture, frame_stride, Th, Tw, uv, mask, H, W, tiles_x, tiles_y, wrap, grad, grad_texture, grad_uv);
+    texture_sample_bwd_kernel<C>
+        <<<dim3((unsigned)((int64_t)B * g.tiles_y * g.tiles_x)), dim3(kLightThreads), 0, stream>>>(
+            texture, frame_stride, Th, Tw, uv, mask, H, W, g.tiles_x, g.tiles_y, wrap, grad, grad_texture, grad_uv);
 }
 
 }  // namespace
@@ -1710,14 +1749,14 @@ int dirt_texture_sample_fwd(const float *texture, int texture_frames, int Th, in
                             const uint8_t *mask, int B, int H, int W, int wrap, float *texels, uint8_t *valid,
                             void *stream_)
 {
-    int64_t n;
-    const int rc = texture_sizes(texture_frames, Th, Tw, B, H, W, C, wrap, &n);
-    if (rc || n == 0) return rc;
+    SampleGrid g;
+    const int rc = texture_sizes(texture_frames, Th, Tw, B, H, W, C, wrap, &g);
+    if (rc || g.pixels == 0) return rc;
     if (!texture || !uv || !texels || !valid) return fail(DIRT_EINVAL, "texture_sample: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int64_t fs = texture_frames == 1 ? 0 : (int64_t)Th * Tw * C, hw = (int64_t)H * W;
     with_each_channel_count(C, [&](auto c) {
-        launch_texture_fwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, hw, n, wrap, texels, valid, stream);
+        launch_texture_fwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, hw, g.pixels, wrap, texels, valid, stream);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
@@ -1727,17 +1766,17 @@ int dirt_texture_sample_bwd(const float *texture, int texture_frames, int Th, in
                             const uint8_t *mask, int B, int H, int W, int wrap, const float *grad_texels,
                             float *grad_texture, float *grad_uv, void *stream_)
 {
-    int64_t n;
-    const int rc = texture_sizes(texture_frames, Th, Tw, B, H, W, C, wrap, &n);
-    if (rc || n == 0 || (!grad_texture && !grad_uv)) return rc;
+    SampleGrid g;
+    const int rc = texture_sizes(texture_frames, Th, Tw, B, H, W, C, wrap, &g);
+    if (rc || g.pixels == 0 || (!grad_texture && !grad_uv)) return rc;
     if (!texture || !uv || !grad_texels) return fail(DIRT_EINVAL, "texture_sample: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int64_t fs = texture_frames == 1 ? 0 : (int64_t)Th * Tw * C;
     if (grad_texture)
         HIP_TRY(hipMemsetAsync(grad_texture, 0, (size_t)texture_frames * Th * Tw * C * sizeof(float), stream));
     with_each_channel_count(C, [&](auto c) {
-        launch_texture_bwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, B, H, W, wrap, grad_texels, grad_texture,
-                                               grad_uv, stream);
+        launch_texture_bwd<decltype(c)::value>(texture, fs, Th, Tw, uv, mask, B, H, W, g, wrap, grad_texels,
+                                               grad_texture, grad_uv, stream);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
@@ -1767,10 +1806,8 @@ int mip_chain_length(int Th, int Tw, int max_levels)
 int mip_sizes(const char *op, int texture_frames, int Th, int Tw, int C, int levels, int *L, int64_t *texels)
 {
     char msg[160];
-    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM) {
-        snprintf(msg, sizeof(msg), "%s: texture height, width must be in 1..%d", op, DIRT_MAX_DIM);
-        return fail(DIRT_EINVAL, msg);
-    }
+    const int rc = texture_dims(op, Th, Tw);
+    if (rc) return rc;
     if (C < 1 || C > DIRT_MAX_CHANNELS) {
         snprintf(msg, sizeof(msg), "%s: expects 1 <= channels <= %d", op, DIRT_MAX_CHANNELS);
         return fail(DIRT_EINVAL, msg);
@@ -1795,23 +1832,13 @@ int mip_sizes(const char *op, int texture_frames, int Th, int Tw, int C, int lev
 }
 
 int mip_sample_sizes(int texture_frames, int Th, int Tw, int C, int levels, int B, int H, int W, int wrap, int *L,
-                     int64_t *texels, int64_t *pixels)
+                     int64_t *texels, SampleGrid *g)
 {
-    int rc = deferred_sizes("texture_sample_mip", B, H, W, C, pixels);
-    if (rc) return rc;
-    const int64_t n = *pixels;
-    *pixels = 0;
-    rc = mip_sizes("texture_sample_mip", texture_frames, Th, Tw, C, levels, L, texels);
-    if (rc) return rc;
-    if (wrap != DIRT_TEXTURE_CLAMP && wrap != DIRT_TEXTURE_REPEAT)
-        return fail(DIRT_EINVAL, "texture_sample_mip: wrap must be DIRT_TEXTURE_CLAMP or DIRT_TEXTURE_REPEAT");
-    if (B > 0 && texture_frames != 1 && texture_frames != B)
-        return fail(DIRT_EINVAL, "texture_sample_mip: texture_frames must be 1 or the batch size");
-    const int64_t tiles = (int64_t)((H + kTexTile - 1) / kTexTile) * ((W + kTexTile - 1) / kTexTile);
-    if ((int64_t)B * tiles > 0x7fffffffLL)
-        return fail(DIRT_EINVAL, "texture_sample_mip: too large (more screen tiles than one launch covers)");
-    *pixels = n;
-    return DIRT_OK;
+    int rc = deferred_sizes("texture_sample_mip", B, H, W, C, &g->pixels);
+    if (!rc) rc = mip_sizes("texture_sample_mip", texture_frames, Th, Tw, C, levels, L, texels);
+    if (!rc) rc = sample_sizes("texture_sample_mip", texture_frames, B, H, W, wrap, g);
+    if (rc) g->pixels = 0;
+    return rc;
 }
 
 template <int C>
@@ -1825,13 +1852,13 @@ void launch_texture_mip_fwd(const float *packed, int64_t frame_stride, int Th, i
 
 template <int C>
 void launch_texture_mip_bwd(const float *packed, int64_t frame_stride, int Th, int Tw, int L, const float *uv,
-                            const uint8_t *mask, const float *lod, int B, int H, int W, int wrap, const float *grad,
-                            float *grad_packed, float *grad_uv, hipStream_t stream)
+                            const uint8_t *mask, const float *lod, int B, int H, int W, SampleGrid g, int wrap,
+                            const float *grad, float *grad_packed, float *grad_uv, hipStream_t stream)
 {
-    const int tiles_x = (W + kTexTile - 1) / kTexTile, tiles_y = (H + kTexTile - 1) / kTexTile;
     texture_sample_mip_bwd_kernel<C>
-        <<<dim3((unsigned)((int64_t)B * tiles_y * tiles_x)), dim3(kLightThreads), 0, stream>>>(
-            packed, frame_stride, Th, Tw, L, uv, mask, lod, H, W, tiles_x, tiles_y, wrap, grad, grad_packed, grad_uv);
+        <<<dim3((unsigned)((int64_t)B * g.tiles_y * g.tiles_x)), dim3(kLightThreads), 0, stream>>>(
+            packed, frame_stride, Th, Tw, L, uv, mask, lod, H, W, g.tiles_x, g.tiles_y, wrap, grad, grad_packed,
+            grad_uv);
 }
 
 }  // namespace
@@ -1840,10 +1867,7 @@ extern "C" {
 
 int dirt_texture_mip_layout(int Th, int Tw, int max_levels, int *dims, long long *offsets, long long *total)
 {
-    if (Th < 1 || Tw < 1 || Th > DIRT_MAX_DIM || Tw > DIRT_MAX_DIM) {
-        (void)fail(DIRT_EINVAL, "texture_mip_layout: texture height, width must be in 1..8192");
-        return 0;
-    }
+    if (texture_dims("texture_mip_layout", Th, Tw)) return 0;
     const int L = mip_chain_length(Th, Tw, max_levels);
     MipLevel lv = mip_level(Th, Tw, 0);
     for (int k = 0; k < L; ++k, lv = mip_next(lv)) {
@@ -1902,16 +1926,17 @@ int dirt_texture_sample_mip_fwd(const float *packed, int texture_frames, int Th,
                                 int W, int wrap, float *texels, uint8_t *valid, float *lod, void *stream_)
 {
     int L;
-    int64_t N, n;
-    const int rc = mip_sample_sizes(texture_frames, Th, Tw, C, levels, B, H, W, wrap, &L, &N, &n);
-    if (rc || n == 0) return rc;
+    int64_t N;
+    SampleGrid g;
+    const int rc = mip_sample_sizes(texture_frames, Th, Tw, C, levels, B, H, W, wrap, &L, &N, &g);
+    if (rc || g.pixels == 0) return rc;
     if (!(lod_bias - lod_bias == 0.0f)) return fail(DIRT_EINVAL, "texture_sample_mip: lod_bias must be finite");
     if (!packed || !uv || !texels || !valid || !lod) return fail(DIRT_EINVAL, "texture_sample_mip: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int64_t fs = texture_frames == 1 ? 0 : N * C;
     with_each_channel_count(C, [&](auto c) {
-        launch_texture_mip_fwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod_in, lod_bias, H, W, n, wrap,
-                                                   texels, valid, lod, stream);
+        launch_texture_mip_fwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod_in, lod_bias, H, W, g.pixels,
+                                                   wrap, texels, valid, lod, stream);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
@@ -1922,15 +1947,16 @@ int dirt_texture_sample_mip_bwd(const float *packed, int texture_frames, int Th,
                                 const float *grad_texels, float *grad_packed, float *grad_uv, void *stream_)
 {
     int L;
-    int64_t N, n;
-    const int rc = mip_sample_sizes(texture_frames, Th, Tw, C, levels, B, H, W, wrap, &L, &N, &n);
-    if (rc || n == 0 || (!grad_packed && !grad_uv)) return rc;
+    int64_t N;
+    SampleGrid g;
+    const int rc = mip_sample_sizes(texture_frames, Th, Tw, C, levels, B, H, W, wrap, &L, &N, &g);
+    if (rc || g.pixels == 0 || (!grad_packed && !grad_uv)) return rc;
     if (!packed || !uv || !lod || !grad_texels) return fail(DIRT_EINVAL, "texture_sample_mip: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int64_t fs = texture_frames == 1 ? 0 : N * C;
     if (grad_packed) HIP_TRY(hipMemsetAsync(grad_packed, 0, (size_t)texture_frames * N * C * sizeof(float), stream));
     with_each_channel_count(C, [&](auto c) {
-        launch_texture_mip_bwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod, B, H, W, wrap, grad_texels,
+        launch_texture_mip_bwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod, B, H, W, g, wrap, grad_texels,
                                                    grad_packed, grad_uv, stream);
     });
     HIP_TRY(hipGetLastError());

@@ -1,6 +1,8 @@
-// Part of dirt_raster.hip's translation unit: included inside its anonymous namespace after deferred_kernels.h
-// (window_max, routed3, pixel_at, finite3, route_any, kRoute*; lighting_kernels.h's ld3 / st3 / dot3 ...,
-// shade_clamp, shade_clamp_grad, spec_terms).  Not a standalone header.
+// Part of dirt_raster.hip's translation unit: included inside its anonymous namespace after deferred_kernels.h.  Not a
+// standalone header.  What it shares with the shade lives there (the route accessors, pixel_at, window_max, routed3,
+// ShadeAdjoint) and in lighting_kernels.h (spec_terms, shade_clamp); the forward's opening, the gather and the
+// per-light adjoints are written out here as in the shade (DESIGN.md 7k has why).  It is not the shade with N = 1: the
+// shade's adjoint sums start at x, these at 0 + x (the sign of a zero), and the parameters are loaded differently.
 //
 // deferred.shade_lights: deferred_kernels.h's shade with up to DIRT_MAX_LIGHTS lights, each directional or a point
 // light, and with gradients to the lights, the camera, the ambient colour and the shininess.  Dilation, `valid` and
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(kLightThreads) void shade_lights_fwd_kernel(
         const PixelAt at = pixel_at(p, H, W);
         float mp[3] = {0.0f, 0.0f, 0.0f}, mn[3] = {0.0f, 0.0f, 0.0f};
         r = window_max<3>(positions, at, H, W, mp);
-        r |= window_max<3>(normals, at, H, W, mn) << 12;
+        r |= window_max<3>(normals, at, H, W, mn) << kRouteNormals;
         pos = make_float3(mp[0], mp[1], mp[2]);
         nv = make_float3(mn[0], mn[1], mn[2]);
     }
@@ -218,7 +220,7 @@ __device__ __forceinline__ SlPixel sl_load_pixel(const float *__restrict__ posit
     const int64_t q = at.f0 + (int64_t)at.y * W + at.x;
     SlPixel x;
     x.pos = routed3(positions, at, H, W, r);
-    x.nv = routed3(normals, at, H, W, r >> 12);
+    x.nv = routed3(normals, at, H, W, route_normals(r));
     x.col = ld3(colors + q * 3);
     x.g = ld3(grad + q * 3);
     return x;
@@ -320,8 +322,8 @@ __global__ __launch_bounds__(kSlThreads) void shade_lights_bwd_kernel(
             float acc[6];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                acc[c] = ((r[k] >> (4 * c)) & 15u) == kRouteOwn ? (&own[k].pos.x)[c] : 0.0f;
-                acc[3 + c] = ((r[k] >> (12 + 4 * c)) & 15u) == kRouteOwn ? (&own[k].nrm.x)[c] : 0.0f;
+                acc[c] = route_code(r[k], c) == kRouteOwn ? (&own[k].pos.x)[c] : 0.0f;
+                acc[3 + c] = route_normal_code(r[k], c) == kRouteOwn ? (&own[k].nrm.x)[c] : 0.0f;
             }
 #pragma unroll 1
             for (int w = 0; w < 9; ++w) {
@@ -341,8 +343,8 @@ __global__ __launch_bounds__(kSlThreads) void shade_lights_bwd_kernel(
                                    shin);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    if (((rq >> (4 * c)) & 15u) == back) acc[c] += (&a.pos.x)[c];
-                    if (((rq >> (12 + 4 * c)) & 15u) == back) acc[3 + c] += (&a.nrm.x)[c];
+                    if (route_code(rq, c) == back) acc[c] += (&a.pos.x)[c];
+                    if (route_normal_code(rq, c) == back) acc[3 + c] += (&a.nrm.x)[c];
                 }
             }
             if (grad_positions) st3(grad_positions + p * 3, make_float3(acc[0], acc[1], acc[2]));

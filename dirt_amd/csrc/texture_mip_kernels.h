@@ -1,5 +1,6 @@
-// Part of dirt_raster.hip's translation unit: included inside its anonymous namespace after texture_kernels.h
-// (TexAxis, tex_axis, tex_sampled, kTexTile, kLightThreads, light_blocks).  Not a standalone header.
+// Part of dirt_raster.hip's translation unit: included inside its anonymous namespace after texture_kernels.h, where
+// every per-level rule lives (its tex_* functions).  Not a standalone header.  Here are the chain, the level of detail,
+// the blend of two levels and a tile's two boxes.
 //
 // Mipmapped deferred texturing: a box-filtered mip chain of a texture [Tf, Th, Tw, C], packed as [Tf, N, C] with the
 // levels in order, each row-major, and the trilinear lookup of that chain at a uv G-buffer [B, H, W, 2].
@@ -25,15 +26,15 @@
 // An explicit lod buffer replaces all of that (a NaN in it becomes 0).  Then lod = lod + lod_bias, clamped to
 // [0, L - 1].  The lod never carries a gradient, neither to the uv nor to an explicit lod.
 //
-// Trilinear: k0 = (int)floor(lod), f = lod - k0, k1 = min(k0 + 1, L - 1); s_k = texture_kernels.h's bilinear rule at
-// level k (T = T_k, the same wrap);  out = s_k0 * (1 - f) + s_k1 * f, and out = s_k0 without reading level k1 when
+// Trilinear: k0 = (int)floor(lod), f = lod - k0, k1 = min(k0 + 1, L - 1); s_k = tex_bilinear at level k (T = T_k, the
+// same wrap);  out = s_k0 * (1 - f) + s_k1 * f, and out = s_k0 without reading level k1 when
 // f == 0.  The forward stores each pixel's final lod ([B, H, W], 0 at unsampled pixels); the backward reads it back.
 //
 // Backward, one launch, a 256-thread workgroup per 16 x 16 screen tile:
-//   grad_uv = grad_uv(k0) * (1 - f) + grad_uv(k1) * f, each term texture_kernels.h's formula with T_k and its pass
-//   rule (f == 0: grad_uv(k0) alone) -- a gather in a fixed order, bit-identical from run to run;
-//   grad_packed[level, tap, c] += g_c * w1 * w2 * wl for the eight taps (wl = 1 - f or f; four taps when f == 0),
-//   float atomics: summed per tile in two LDS patches first (the tile's lowest level and the one above it) where
+//   grad_uv = grad_uv(k0) * (1 - f) + grad_uv(k1) * f, each term tex_grad_uv with T_k (f == 0: grad_uv(k0) alone) -- a
+//   gather in a fixed order, bit-identical from run to run;
+//   grad_packed[level, tap, c] += g_c * w1 * w2 * wl, tex_add_taps with wl = 1 - f or f (four taps when f == 0), float
+//   atomics: summed per tile in two LDS patches first (the tile's lowest level and the one above it) where
 //   their boxes fit, straight to memory otherwise (see the kernel).
 // Every packed offset is formed in 64 bits.
 
@@ -190,21 +191,6 @@ __device__ __forceinline__ MipPick mip_pick(float lod, int Th, int Tw, int L)
 }
 
 template <int C>
-__device__ __forceinline__ void mip_bilinear(const float *__restrict__ t, int Tw, const TexAxis &ax, const TexAxis &ay,
-                                             float *out)
-{
-    const float *t00 = t + ((int64_t)ay.i0 * Tw + ax.i0) * C, *t01 = t + ((int64_t)ay.i0 * Tw + ax.i1) * C;
-    const float *t10 = t + ((int64_t)ay.i1 * Tw + ax.i0) * C, *t11 = t + ((int64_t)ay.i1 * Tw + ax.i1) * C;
-    const float a = ax.a, b = ay.a, oma = 1.0f - a, omb = 1.0f - b;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float top = t00[c] * oma + t01[c] * a;
-        const float bot = t10[c] * oma + t11[c] * a;
-        out[c] = top * omb + bot * b;
-    }
-}
-
-template <int C>
 __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_fwd_kernel(
     const float *__restrict__ packed, int64_t frame_stride, int Th, int Tw, int L, const float *__restrict__ uv,
     const uint8_t *__restrict__ mask, const float *__restrict__ lod_in, float lod_bias, int H, int W, int64_t n,
@@ -230,10 +216,10 @@ __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_fwd_kernel(
         lod = mip_final_lod(lod, lod_bias, L);
         const MipPick pk = mip_pick(lod, Th, Tw, L);
         const float *t = packed + (row / H) * frame_stride;
-        mip_bilinear<C>(t + pk.l0.off * C, pk.l0.w, tex_axis(u, pk.l0.w, wrap), tex_axis(v, pk.l0.h, wrap), out);
+        tex_bilinear<C>(t + pk.l0.off * C, pk.l0.w, tex_axis(u, pk.l0.w, wrap), tex_axis(v, pk.l0.h, wrap), out);
         if (pk.f != 0.0f) {
             float s1[C];
-            mip_bilinear<C>(t + pk.l1.off * C, pk.l1.w, tex_axis(u, pk.l1.w, wrap), tex_axis(v, pk.l1.h, wrap), s1);
+            tex_bilinear<C>(t + pk.l1.off * C, pk.l1.w, tex_axis(u, pk.l1.w, wrap), tex_axis(v, pk.l1.h, wrap), s1);
             const float omf = 1.0f - pk.f;
 #pragma unroll
             for (int c = 0; c < C; ++c) out[c] = out[c] * omf + s1[c] * pk.f;
@@ -243,53 +229,6 @@ __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_fwd_kernel(
     for (int c = 0; c < C; ++c) texels[p * C + c] = out[c];
     valid[p] = ok ? 1 : 0;
     lod_out[p] = lod;
-}
-
-// One level's uv gradient of a pixel (texture_kernels.h's formula with the level's dimensions); t points at the
-// level's first float in the pixel's frame.
-template <int C>
-__device__ __forceinline__ void mip_level_uv(const float *__restrict__ t, int h, int w, float u, float v, int wrap,
-                                             const float *g, float *gu, float *gv)
-{
-    const TexAxis ax = tex_axis(u, w, wrap), ay = tex_axis(v, h, wrap);
-    const float a = ax.a, b = ay.a, oma = 1.0f - a, omb = 1.0f - b;
-    const int64_t o00 = ((int64_t)ay.i0 * w + ax.i0) * C, o01 = ((int64_t)ay.i0 * w + ax.i1) * C;
-    const int64_t o10 = ((int64_t)ay.i1 * w + ax.i0) * C, o11 = ((int64_t)ay.i1 * w + ax.i1) * C;
-    float su = 0.0f, sv = 0.0f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float t00 = t[o00 + c], t01 = t[o01 + c], t10 = t[o10 + c], t11 = t[o11 + c];
-        const float du = (t01 - t00) * omb + (t11 - t10) * b;
-        const float top = t00 * oma + t01 * a;
-        const float bot = t10 * oma + t11 * a;
-        su += g[c] * du;  // (the first sum adds to +0: exact)
-        sv += g[c] * (bot - top);
-    }
-    *gu = ax.pass ? (float)w * su : 0.0f;
-    *gv = ay.pass ? (float)h * sv : 0.0f;
-}
-
-// the four taps of one level of one lane, added with the level weight wl to dst: the level's first float in global
-// memory (bw = the level's width, r0 = c0 = 0) or an LDS patch over the box of rows r0.., columns c0.., bw wide
-template <int C>
-__device__ __forceinline__ void mip_add_taps(float *dst, int r0, int c0, int bw, const TexAxis &ax, const TexAxis &ay,
-                                             const float *g, float wl)
-{
-    const float a = ax.a, b = ay.a, oma = 1.0f - a, omb = 1.0f - b;
-    const int64_t o00 = ((int64_t)(ay.i0 - r0) * bw + (ax.i0 - c0)) * C,
-                  o01 = ((int64_t)(ay.i0 - r0) * bw + (ax.i1 - c0)) * C;
-    const int64_t o10 = ((int64_t)(ay.i1 - r0) * bw + (ax.i0 - c0)) * C,
-                  o11 = ((int64_t)(ay.i1 - r0) * bw + (ax.i1 - c0)) * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        atomicAdd(dst + o00 + c, g[c] * oma * omb * wl);
-        atomicAdd(dst + o01 + c, g[c] * a * omb * wl);
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        atomicAdd(dst + o10 + c, g[c] * oma * b * wl);
-        atomicAdd(dst + o11 + c, g[c] * a * b * wl);
-    }
 }
 
 #ifndef DIRT_TEXTURE_MIP_PATCH
@@ -303,10 +242,9 @@ constexpr int kMipPatchTexels = DIRT_TEXTURE_MIP_PATCH;
 // One workgroup per 16 x 16 screen tile of one frame (blockIdx.x = (frame * tiles_y + tile_y) * tiles_x + tile_x): a
 // tile's lanes share their levels and a compact texel footprint.  grad_uv first, a gather per lane.  Then the tile
 // takes its lowest k0 (level A) and the level above it (B), reduces the boxes of its lanes' taps at A (lanes with
-// k0 = A) and at B (their second level, and the first level of lanes with k0 = B) as texture_kernels.h does; the boxes
-// share kMipPatchTexels texels of LDS, A served first, B from what A leaves.  A box that fits sums its taps in LDS
-// (ds_add_f32) and adds the patch's nonzero elements to memory once, consecutive lanes on consecutive floats of a
-// texel row.  Taps at any other level, and those of a box that does not fit, go straight to memory.
+// k0 = A) and at B (their second level, and the first level of lanes with k0 = B), tex_box_reduce each; the boxes
+// share kMipPatchTexels texels of LDS, A served first, B from what A leaves.  A box that fits sums its taps in LDS and
+// is flushed as the plain kernel's.  Taps at any other level, and those of a box that does not fit, go to memory.
 template <int C>
 __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_bwd_kernel(
     const float *__restrict__ packed, int64_t frame_stride, int Th, int Tw, int L, const float *__restrict__ uv,
@@ -342,10 +280,12 @@ __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_bwd_kernel(
         float gu = 0.0f, gv = 0.0f;
         if (ok) {
             const float *t = packed + fbase;
-            mip_level_uv<C>(t + pk.l0.off * C, pk.l0.h, pk.l0.w, u, v, wrap, g, &gu, &gv);
+            tex_grad_uv<C>(t + pk.l0.off * C, pk.l0.h, pk.l0.w, tex_axis(u, pk.l0.w, wrap),
+                           tex_axis(v, pk.l0.h, wrap), g, &gu, &gv);
             if (two) {
                 float gu1, gv1;
-                mip_level_uv<C>(t + pk.l1.off * C, pk.l1.h, pk.l1.w, u, v, wrap, g, &gu1, &gv1);
+                tex_grad_uv<C>(t + pk.l1.off * C, pk.l1.h, pk.l1.w, tex_axis(u, pk.l1.w, wrap),
+                               tex_axis(v, pk.l1.h, wrap), g, &gu1, &gv1);
                 gu = gu * omf + gu1 * pk.f;
                 gv = gv * omf + gv1 * pk.f;
             }
@@ -356,11 +296,7 @@ __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_bwd_kernel(
     if (!grad_packed) return;  // (uniform)
 
     float *gp = grad_packed + fbase;
-    TexAxis ax0, ay0, ax1, ay1;
-    ax0.i0 = ax0.i1 = ay0.i0 = ay0.i1 = 0;
-    ax0.a = ay0.a = 0.0f;
-    ax0.pass = ay0.pass = false;
-    ax1 = ay1 = ax0;
+    TexAxis ax0 = kTexNoAxis, ay0 = ax0, ax1 = ax0, ay1 = ax0;
     if (ok) {
         ax0 = tex_axis(u, pk.l0.w, wrap);
         ay0 = tex_axis(v, pk.l0.h, wrap);
@@ -372,37 +308,20 @@ __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_bwd_kernel(
     const float w0 = two ? omf : 1.0f;
 
     if (kMipPatchTexels > 0) {
-        const int big = 0x7fffffff;
-        if (threadIdx.x < 9) s_box[threadIdx.x] = big;
+        if (threadIdx.x < 9) s_box[threadIdx.x] = kTexBoxEmpty;
         __syncthreads();
-        const int kmin_w = wave_min(ok ? pk.k0 : big);
+        const int kmin_w = wave_min(ok ? pk.k0 : kTexBoxEmpty);
         if ((threadIdx.x & 63) == 0) atomicMin(&s_box[0], kmin_w);
         __syncthreads();
         const int kA = s_box[0];
-        if (kA == big) return;  // no sampled pixel in the tile (uniform)
+        if (kA == kTexBoxEmpty) return;  // no sampled pixel in the tile (uniform)
         // this lane's taps at level A and at level B
         const bool hasA = ok && pk.k0 == kA, firstB = ok && pk.k0 == kA + 1, hasB = firstB || (hasA && two);
-        const TexAxis &bx = firstB ? ax0 : ax1, &by = firstB ? ay0 : ay1;
-        {
-            // i0 <= i1 and j0 <= j1 in clamp mode; on the repeat seam they swap, so both orders enter the box
-            const int a0 = wave_min(hasA ? min(ay0.i0, ay0.i1) : big), a1 = wave_min(hasA ? -max(ay0.i0, ay0.i1) : big);
-            const int a2 = wave_min(hasA ? min(ax0.i0, ax0.i1) : big), a3 = wave_min(hasA ? -max(ax0.i0, ax0.i1) : big);
-            const int b0 = wave_min(hasB ? min(by.i0, by.i1) : big), b1 = wave_min(hasB ? -max(by.i0, by.i1) : big);
-            const int b2 = wave_min(hasB ? min(bx.i0, bx.i1) : big), b3 = wave_min(hasB ? -max(bx.i0, bx.i1) : big);
-            if ((threadIdx.x & 63) == 0) {
-                atomicMin(&s_box[1], a0);
-                atomicMin(&s_box[2], a1);
-                atomicMin(&s_box[3], a2);
-                atomicMin(&s_box[4], a3);
-                atomicMin(&s_box[5], b0);
-                atomicMin(&s_box[6], b1);
-                atomicMin(&s_box[7], b2);
-                atomicMin(&s_box[8], b3);
-            }
-        }
+        tex_box_reduce(hasA, ax0, ay0, s_box + 1);
+        tex_box_reduce(hasB, firstB ? ax0 : ax1, firstB ? ay0 : ay1, s_box + 5);
         __syncthreads();
         const int rA = s_box[1], cA = s_box[3], hA = -s_box[2] - rA + 1, wA = -s_box[4] - cA + 1;
-        const bool anyB = s_box[5] != big;
+        const bool anyB = s_box[5] != kTexBoxEmpty;
         const int rB = anyB ? s_box[5] : 0, cB = anyB ? s_box[7] : 0;
         const int hB = anyB ? -s_box[6] - rB + 1 : 0, wB = anyB ? -s_box[8] - cB + 1 : 0;
         // A takes the budget first, B what A leaves: a tile whose finer box is too large still sums the coarser one
@@ -412,29 +331,28 @@ __global__ __launch_bounds__(kLightThreads) void texture_sample_mip_bwd_kernel(
             const int eA = inA ? (int)nA * C : 0, eB = inB ? (int)nB * C : 0;
             for (int e = threadIdx.x; e < eA + eB; e += kLightThreads) s_patch[e] = 0.0f;
             __syncthreads();
-            if (hasA && inA) mip_add_taps<C>(s_patch, rA, cA, wA, ax0, ay0, g, w0);
-            else if (firstB && inB) mip_add_taps<C>(s_patch + eA, rB, cB, wB, ax0, ay0, g, w0);
-            else if (ok) mip_add_taps<C>(gp + pk.l0.off * C, 0, 0, pk.l0.w, ax0, ay0, g, w0);
+            if (hasA && inA) tex_add_taps<C>(s_patch, rA, cA, wA, ax0, ay0, g, w0);
+            else if (firstB && inB) tex_add_taps<C>(s_patch + eA, rB, cB, wB, ax0, ay0, g, w0);
+            else if (ok) tex_add_taps<C>(gp + pk.l0.off * C, 0, 0, pk.l0.w, ax0, ay0, g, w0);
             if (two) {
-                if (hasA && inB) mip_add_taps<C>(s_patch + eA, rB, cB, wB, ax1, ay1, g, pk.f);
-                else mip_add_taps<C>(gp + pk.l1.off * C, 0, 0, pk.l1.w, ax1, ay1, g, pk.f);
+                if (hasA && inB) tex_add_taps<C>(s_patch + eA, rB, cB, wB, ax1, ay1, g, pk.f);
+                else tex_add_taps<C>(gp + pk.l1.off * C, 0, 0, pk.l1.w, ax1, ay1, g, pk.f);
             }
             __syncthreads();
-            // flush: consecutive lanes on consecutive floats of a texel row
+            // flush, both patches in one pass over their eA + eB floats (a tex_flush_patch per box costs 6 SGPRs)
             const MipLevel lA = mip_level(Th, Tw, kA), lB = mip_next(lA);
             for (int e = threadIdx.x; e < eA + eB; e += kLightThreads) {
                 const float s = s_patch[e];
                 if (s != 0.0f) {
                     const bool second = e >= eA;
-                    const int q = second ? e - eA : e, run = (second ? wB : wA) * C, row = q / run;
                     const MipLevel &lv = second ? lB : lA;
-                    atomicAdd(gp + (lv.off + (int64_t)((second ? rB : rA) + row) * lv.w + (second ? cB : cA)) * C +
-                                  (q - row * run), s);
+                    tex_flush_add<C>(s, second ? e - eA : e, second ? rB : rA, second ? cB : cA, second ? wB : wA,
+                                     gp + lv.off * C, lv.w);
                 }
             }
             return;
         }
     }
-    if (ok) mip_add_taps<C>(gp + pk.l0.off * C, 0, 0, pk.l0.w, ax0, ay0, g, w0);
-    if (two) mip_add_taps<C>(gp + pk.l1.off * C, 0, 0, pk.l1.w, ax1, ay1, g, pk.f);
+    if (ok) tex_add_taps<C>(gp + pk.l0.off * C, 0, 0, pk.l0.w, ax0, ay0, g, w0);
+    if (two) tex_add_taps<C>(gp + pk.l1.off * C, 0, 0, pk.l1.w, ax1, ay1, g, pk.f);
 }

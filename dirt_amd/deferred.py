@@ -68,6 +68,46 @@ def _no_double_backward(fn):
                            "set DIRT_FUSED_DEFERRED=0 to use the framework-op statement" % fn)
 
 
+def _batched(x, dim=4):
+    """x contiguous with `dim` dimensions, a leading one added where it has one fewer, and whether it was added."""
+    x = x.contiguous()
+    return (x, False) if x.dim() == dim else (x[None], True)
+
+
+def _unbatched(results, added):
+    """a result or a tuple of results, without the batch dimension that `_batched` added"""
+    if not added:
+        return results
+    return results[0] if isinstance(results, torch.Tensor) else tuple(r[0] for r in results)
+
+
+def _checked_mask(fn, mask, like, name):
+    """mask (or None) as a tensor on like's device, of like's shape without the channels"""
+    if mask is not None:
+        mask = torch.as_tensor(mask, device=like.device)
+        if mask.shape != like.shape[:-1]:
+            raise ValueError("%s: mask of shape %s for %s of shape %s"
+                             % (fn, tuple(mask.shape), name, tuple(like.shape)))
+    return mask
+
+
+def _kernel_mask(mask, batched):
+    """mask (or None) as the kernels read it: uint8 0 / 1 over the pixels of the batched operand"""
+    if mask is None:
+        return None
+    return (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8).reshape(batched.shape[:-1])
+
+
+def _gbuffers(fn, positions, colors, normals):
+    """the three G-buffers as tensors of positions' dtype and device, their shapes checked"""
+    positions = torch.as_tensor(positions)
+    colors, normals = (torch.as_tensor(x, dtype=positions.dtype, device=positions.device) for x in (colors, normals))
+    if positions.dim() not in (3, 4) or positions.shape[-1] != 3 or colors.shape != positions.shape or \
+            normals.shape != positions.shape:
+        raise ValueError("%s: positions, colors, normals must share one shape [H, W, 3] or [B, H, W, 3]" % fn)
+    return positions, colors, normals
+
+
 # ---- dilation
 
 def _dilate_ops(x, mask=None):
@@ -111,31 +151,30 @@ def dilate(x, mask=None):
     x = torch.as_tensor(x)
     if x.dim() not in (3, 4):
         raise ValueError("dilate: x must be [H, W, C] or [B, H, W, C]")
-    if mask is not None:
-        mask = torch.as_tensor(mask, device=x.device)
-        if mask.shape != x.shape[:-1]:
-            raise ValueError("dilate: mask of shape %s for x of shape %s" % (tuple(mask.shape), tuple(x.shape)))
+    mask = _checked_mask("dilate", mask, x, "x")
     if (_FUSED_ENABLED and _gpu_f32(x) and 1 <= x.shape[-1] <= _lib.MAX_CHANNELS and
             (mask is None or mask.device == x.device)):
-        xb = x.contiguous() if x.dim() == 4 else x.contiguous()[None]
-        mb = None
-        if mask is not None:
-            mb = (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8)
-        out = _DilateFn.apply(xb, mb)
-        return out if x.dim() == 4 else out[0]
+        xb, added = _batched(x)
+        return _unbatched(_DilateFn.apply(xb, _kernel_mask(mask, xb)), added)
     return _dilate_ops(x, mask)
 
 
 # ---- shade
 
-def _shade_ops(positions, colors, normals, ambient_color, light_direction, diffuse_color, specular_color,
-               camera_position, shininess, double_sided=False):
-    dev, dt = positions.device, positions.dtype
+def _dilated_gbuffers(positions, colors, normals):
+    """The statement's opening: positions and normals dilated under the positions' background, `valid` where both are
+    finite, and the three G-buffers zero-filled elsewhere -> (positions, normals, colors, valid)."""
     bg = torch.isinf(positions).any(-1)
     pos_d = _dilate_ops(positions, bg)
     nrm_d = _dilate_ops(normals, bg)
     valid = torch.isfinite(pos_d).all(-1, keepdim=True) & torch.isfinite(nrm_d).all(-1, keepdim=True)
-    pos_s, nrm_s, col_s = (torch.where(valid, x, 0.0) for x in (pos_d, nrm_d, colors))
+    return tuple(torch.where(valid, x, 0.0) for x in (pos_d, nrm_d, colors)) + (valid,)
+
+
+def _shade_ops(positions, colors, normals, ambient_color, light_direction, diffuse_color, specular_color,
+               camera_position, shininess, double_sided=False):
+    dev, dt = positions.device, positions.dtype
+    pos_s, nrm_s, col_s, valid = _dilated_gbuffers(positions, colors, normals)
     ambient = col_s * torch.as_tensor(ambient_color, dtype=dt, device=dev)
     diffuse = _diffuse_directional_ops(nrm_s.reshape(-1, 3), col_s.reshape(-1, 3), light_direction, diffuse_color,
                                        double_sided)
@@ -194,19 +233,13 @@ def shade(positions, colors, normals, ambient_color, light_direction, diffuse_co
 
     Returns (pixels, valid): valid [..., H, W, 1] bool marks the pixels whose dilated position and normal are finite;
     the others shade to exactly 0 and carry no gradient."""
-    positions = torch.as_tensor(positions)
-    dev, dt = positions.device, positions.dtype
-    colors, normals = (torch.as_tensor(x, dtype=dt, device=dev) for x in (colors, normals))
-    if positions.dim() not in (3, 4) or positions.shape[-1] != 3 or colors.shape != positions.shape or \
-            normals.shape != positions.shape:
-        raise ValueError("shade: positions, colors, normals must share one shape [H, W, 3] or [B, H, W, 3]")
+    positions, colors, normals = _gbuffers("shade", positions, colors, normals)
     if _FUSED_ENABLED and _gpu_f32(positions, colors, normals) and isinstance(shininess, (int, float)):
         ps = [_light_param(x, positions) for x in (ambient_color, light_direction, diffuse_color, specular_color,
                                                    camera_position)]
         if all(p is not None for p in ps):
-            ops = [x.contiguous() if x.dim() == 4 else x.contiguous()[None] for x in (positions, colors, normals)]
-            pixels, valid = _ShadeFn.apply(*ops, *ps, float(shininess), 1 if double_sided else 0)
-            return (pixels, valid) if positions.dim() == 4 else (pixels[0], valid[0])
+            ops, added = zip(*(_batched(x) for x in (positions, colors, normals)))
+            return _unbatched(_ShadeFn.apply(*ops, *ps, float(shininess), 1 if double_sided else 0), added[0])
     return _shade_ops(positions, colors, normals, ambient_color, light_direction, diffuse_color, specular_color,
                       camera_position, shininess, double_sided)
 
@@ -231,12 +264,9 @@ def _shade_lights_ops(positions, colors, normals, light_vectors, diffuse_colors,
     """The framework-op statement of shade_lights: light arrays [N,3] or [B,N,3], camera [3] or [B,3]."""
     dev, dt = positions.device, positions.dtype
     as_t = lambda x: torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
-    bg = torch.isinf(positions).any(-1)
-    pos_d = _dilate_ops(positions, bg)
-    nrm_d = _dilate_ops(normals, bg)
-    valid = torch.isfinite(pos_d).all(-1, keepdim=True) & torch.isfinite(nrm_d).all(-1, keepdim=True)
+    *buffers, valid = _dilated_gbuffers(positions, colors, normals)
     frames = positions.shape[0] if positions.dim() == 4 else 1
-    pos_s, nrm_s, col_s = (torch.where(valid, x, 0.0).reshape(frames, -1, 3) for x in (pos_d, nrm_d, colors))
+    pos_s, nrm_s, col_s = (x.reshape(frames, -1, 3) for x in buffers)
     vectors, diffuse, specular, camera = (as_t(x) for x in (light_vectors, diffuse_colors, specular_colors,
                                                             camera_position))
     if isinstance(shininess, torch.Tensor):
@@ -356,12 +386,8 @@ def shade_lights(positions, colors, normals, light_vectors, diffuse_colors, spec
     need gradients: the G-buffers, the light arrays, the camera, the ambient colour and a tensor shininess.  A
     parameter's gradient is the sum of its per-pixel terms in a fixed order: bit-identical from run to run."""
     fn = "shade_lights"
-    positions = torch.as_tensor(positions)
+    positions, colors, normals = _gbuffers(fn, positions, colors, normals)
     dev, dt = positions.device, positions.dtype
-    colors, normals = (torch.as_tensor(x, dtype=dt, device=dev) for x in (colors, normals))
-    if positions.dim() not in (3, 4) or positions.shape[-1] != 3 or colors.shape != positions.shape or \
-            normals.shape != positions.shape:
-        raise ValueError("%s: positions, colors, normals must share one shape [H, W, 3] or [B, H, W, 3]" % fn)
     lights = [x if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=dt, device=dev)
               for x in (light_vectors, diffuse_colors, specular_colors)]
     if any(x.dim() not in (2, 3) or x.shape[-1] != 3 for x in lights):
@@ -393,12 +419,11 @@ def shade_lights(positions, colors, normals, light_vectors, diffuse_colors, spec
         ps.append(_lights_param(camera_position, positions, ((3,), (frames, 3))))
         amb = None if ambient_color is None else _lights_param(ambient_color, positions, ((3,),))
         if all(p is not None for p in ps) and (ambient_color is None or amb is not None):
-            ops = [x.contiguous() if x.dim() == 4 else x.contiguous()[None] for x in (positions, colors, normals)]
+            ops, added = zip(*(_batched(x) for x in (positions, colors, normals)))
             number = isinstance(shininess, (int, float))
-            pixels, valid = _ShadeLightsFn.apply(*ops, *ps, amb, None if number else shininess.contiguous(),
-                                                 float(shininess) if number else 0.0, _point_mask(point),
-                                                 1 if double_sided else 0)
-            return (pixels, valid) if positions.dim() == 4 else (pixels[0], valid[0])
+            return _unbatched(_ShadeLightsFn.apply(*ops, *ps, amb, None if number else shininess.contiguous(),
+                                                   float(shininess) if number else 0.0, _point_mask(point),
+                                                   1 if double_sided else 0), added[0])
     return _shade_lights_ops(positions, colors, normals, lights[0], lights[1], lights[2], camera_position, shininess,
                              ambient_color, point, double_sided)
 
@@ -424,19 +449,25 @@ def _texture_axis(u, T, wrap):
     return torch.clamp(j0, 0, T - 1), torch.clamp(j1, 0, T - 1), a
 
 
-def _sample_texture_ops(texture, uv, mask=None, wrap="clamp"):
-    """texture [Th,Tw,C] or [B,Th,Tw,C], uv [H,W,2] or [B,H,W,2], mask (uv's shape without the channels) or None."""
+def _gather_taps(texture, uv, sampled, wrap):
+    """The four taps ([...,C]) of the pixels in `sampled` and the weights of the second column and row ([...,1]):
+    (t00, t01, t10, t11, a, b); texture [Th,Tw,C] or [B,Th,Tw,C]."""
     Th, Tw = texture.shape[-3], texture.shape[-2]
-    valid = torch.isfinite(uv).all(-1) if mask is None else mask != 0
-    uvs = torch.where(valid[..., None], uv, 0.0)  # (no index is ever formed from an unsampled pixel's uv)
+    uvs = torch.where(sampled[..., None], uv, 0.0)  # (no index is ever formed from an unsampled pixel's uv)
     j0, j1, a = _texture_axis(uvs[..., 0], Tw, wrap)
     i0, i1, b = _texture_axis(uvs[..., 1], Th, wrap)
     if texture.dim() == 4:
         f = torch.arange(texture.shape[0], device=texture.device)[:, None, None]
-        t00, t01, t10, t11 = texture[f, i0, j0], texture[f, i0, j1], texture[f, i1, j0], texture[f, i1, j1]
+        taps = texture[f, i0, j0], texture[f, i0, j1], texture[f, i1, j0], texture[f, i1, j1]
     else:
-        t00, t01, t10, t11 = texture[i0, j0], texture[i0, j1], texture[i1, j0], texture[i1, j1]
-    a, b = a[..., None], b[..., None]
+        taps = texture[i0, j0], texture[i0, j1], texture[i1, j0], texture[i1, j1]
+    return taps + (a[..., None], b[..., None])
+
+
+def _sample_texture_ops(texture, uv, mask=None, wrap="clamp"):
+    """texture [Th,Tw,C] or [B,Th,Tw,C], uv [H,W,2] or [B,H,W,2], mask (uv's shape without the channels) or None."""
+    valid = torch.isfinite(uv).all(-1) if mask is None else mask != 0
+    t00, t01, t10, t11, a, b = _gather_taps(texture, uv, valid, wrap)
     oma, omb = 1.0 - a, 1.0 - b
     top = t00 * oma + t01 * a
     bot = t10 * oma + t11 * a
@@ -505,22 +536,13 @@ def sample_texture(texture, uv, mask=None, wrap="clamp"):
     if texture.dim() == 4 and (uv.dim() != 4 or texture.shape[0] != uv.shape[0]):
         raise ValueError("sample_texture: a per-frame texture of shape %s for uv of shape %s"
                          % (tuple(texture.shape), tuple(uv.shape)))
-    if mask is not None:
-        mask = torch.as_tensor(mask, device=uv.device)
-        if mask.shape != uv.shape[:-1]:
-            raise ValueError("sample_texture: mask of shape %s for uv of shape %s"
-                             % (tuple(mask.shape), tuple(uv.shape)))
+    mask = _checked_mask("sample_texture", mask, uv, "uv")
     if (_FUSED_ENABLED and _gpu_f32(texture, uv) and 1 <= texture.shape[-1] <= _lib.MAX_CHANNELS and
             max(texture.shape[-3], texture.shape[-2]) <= _lib.MAX_DIM and
             1 <= min(uv.shape[-3:-1]) and max(uv.shape[-3:-1]) <= _lib.MAX_DIM and
             (mask is None or mask.device == uv.device)):
-        tb = texture.contiguous() if texture.dim() == 4 else texture.contiguous()[None]
-        ub = uv.contiguous() if uv.dim() == 4 else uv.contiguous()[None]
-        mb = None
-        if mask is not None:
-            mb = (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8).reshape(ub.shape[:-1])
-        texels, valid = _SampleTextureFn.apply(tb, ub, mb, _WRAPS[wrap])
-        return (texels, valid) if uv.dim() == 4 else (texels[0], valid[0])
+        (tb, _), (ub, added) = _batched(texture), _batched(uv)
+        return _unbatched(_SampleTextureFn.apply(tb, ub, _kernel_mask(mask, ub), _WRAPS[wrap]), added)
     return _sample_texture_ops(texture, uv, mask, wrap)
 
 
@@ -627,9 +649,8 @@ def build_mipmaps(texture, levels=None):
         raise ValueError("build_mipmaps: levels must be a positive integer or None")
     if _FUSED_ENABLED and _gpu_f32(texture) and _mip_fused_texture(texture.shape):
         dims = _mip_dims(texture.shape[-3], texture.shape[-2], levels)
-        tb = texture.contiguous() if texture.dim() == 4 else texture.contiguous()[None]
-        packed = _BuildMipmapsFn.apply(tb, len(dims))
-        return Mipmaps(packed if texture.dim() == 4 else packed[0], dims[0][0], dims[0][1], len(dims))
+        tb, added = _batched(texture)
+        return Mipmaps(_unbatched(_BuildMipmapsFn.apply(tb, len(dims)), added), dims[0][0], dims[0][1], len(dims))
     return _build_mipmaps_ops(texture, levels)
 
 
@@ -703,16 +724,7 @@ class _BilinearFn(torch.autograd.Function):
 def _mip_level_ops(texture, uv, sampled, wrap):
     """`_sample_texture_ops`' rule at one level, for the pixels in `sampled`; the value is the rule's bit for bit, the
     uv gradient is in the kernels' difference form (`_BilinearFn`), and it differentiates again."""
-    Th, Tw = texture.shape[-3], texture.shape[-2]
-    uvs = torch.where(sampled[..., None], uv, 0.0)  # (no index is ever formed from an unsampled pixel's uv)
-    j0, j1, a = _texture_axis(uvs[..., 0], Tw, wrap)
-    i0, i1, b = _texture_axis(uvs[..., 1], Th, wrap)
-    if texture.dim() == 4:
-        f = torch.arange(texture.shape[0], device=texture.device)[:, None, None]
-        t00, t01, t10, t11 = texture[f, i0, j0], texture[f, i0, j1], texture[f, i1, j0], texture[f, i1, j1]
-    else:
-        t00, t01, t10, t11 = texture[i0, j0], texture[i0, j1], texture[i1, j0], texture[i1, j1]
-    out = _BilinearFn.apply(t00, t01, t10, t11, a[..., None], b[..., None])
+    out = _BilinearFn.apply(*_gather_taps(texture, uv, sampled, wrap))
     return torch.where(sampled[..., None], out, 0.0)
 
 
@@ -795,10 +807,7 @@ def _sample_texture_mip(mipmaps, uv, mask=None, wrap="clamp", lod=None, lod_bias
     if packed.dim() == 3 and (uv.dim() != 4 or packed.shape[0] != uv.shape[0]):
         raise ValueError("%s: a per-frame chain of shape %s for uv of shape %s"
                          % (fn, tuple(packed.shape), tuple(uv.shape)))
-    if mask is not None:
-        mask = torch.as_tensor(mask, device=uv.device)
-        if mask.shape != uv.shape[:-1]:
-            raise ValueError("%s: mask of shape %s for uv of shape %s" % (fn, tuple(mask.shape), tuple(uv.shape)))
+    mask = _checked_mask(fn, mask, uv, "uv")
     if lod is not None:
         lod = torch.as_tensor(lod, device=uv.device)
         if lod.shape != uv.shape[:-1] or not lod.is_floating_point():
@@ -811,15 +820,10 @@ def _sample_texture_mip(mipmaps, uv, mask=None, wrap="clamp", lod=None, lod_bias
     if (_FUSED_ENABLED and _gpu_f32(packed, uv) and _mip_fused_texture((Th, Tw, packed.shape[-1])) and
             L <= _lib.MAX_MIP_LEVELS and 1 <= min(uv.shape[-3:-1]) and max(uv.shape[-3:-1]) <= _lib.MAX_DIM and
             (mask is None or mask.device == uv.device)):
-        pb = packed.contiguous() if packed.dim() == 3 else packed.contiguous()[None]
-        ub = uv.contiguous() if uv.dim() == 4 else uv.contiguous()[None]
-        mb = lb = None
-        if mask is not None:
-            mb = (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8).reshape(ub.shape[:-1])
-        if lod is not None:
-            lb = lod.detach().to(torch.float32).contiguous().reshape(ub.shape[:-1])
-        texels, valid, lod_out = _SampleTextureMipFn.apply(pb, ub, mb, lb, Th, Tw, L, _WRAPS[wrap], lod_bias)
-        return (texels, valid, lod_out) if uv.dim() == 4 else (texels[0], valid[0], lod_out[0])
+        (pb, _), (ub, added) = _batched(packed, 3), _batched(uv)
+        lb = None if lod is None else lod.detach().to(torch.float32).contiguous().reshape(ub.shape[:-1])
+        return _unbatched(_SampleTextureMipFn.apply(pb, ub, _kernel_mask(mask, ub), lb, Th, Tw, L, _WRAPS[wrap],
+                                                    lod_bias), added)
     return _sample_texture_mip_ops(mipmaps, uv, mask, wrap, lod, lod_bias)
 
 

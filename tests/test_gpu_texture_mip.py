@@ -20,6 +20,7 @@ import torch
 
 import deferred_cases as dc
 import deferred_pipeline as dp
+import texture_cases as tc
 import texture_mip_cases as mc
 from dirt_amd import deferred
 
@@ -161,6 +162,49 @@ def test_exact_scatter(kind, C, frames):
     assert np.array_equal(got["grad_texture"].astype(np.float64), vjp["grad_texture"]), kind
     assert np.count_nonzero(vjp["grad_texture"]) > 0
     _check_grads(got, inp, vjp, kind)
+
+
+@pytest.mark.parametrize("wrap", ["clamp", "repeat"])
+@pytest.mark.parametrize("kind,C,frames", [("magnify16", 3, 1), ("scatter", 8, 2)])
+def test_one_level_is_sample_texture(kind, C, frames, wrap):
+    """The GPU form of test_texture_mip_cpu.py's test of this name, and the pin of what the two headers share: over a
+    one-level chain the mip kernels are the plain kernels' per-level functions called once, so texels, valid, grad_uv
+    and grad_texture equal sample_texture's bit for bit, every element -- with the lod taken from the uv differences,
+    and with an explicit random lod and a lod_bias (both clamp to level 0).  texture_cases.exact_scatter_case: every
+    product and partial sum is exact in float32, so the order of the atomics cannot excuse a difference; magnify16
+    goes through both kernels' LDS patches, scatter through their direct atomics."""
+    (texture, uv, mask, _, grad), fwd, vjp = tc.exact_scatter_case(kind, C, frames)
+    assert uv.shape == (frames, 63, 65, 2) and texture.shape == (64, 64, C)
+    assert np.count_nonzero(vjp["grad_texture"]) > 0 and np.count_nonzero(vjp["grad_uv"]) > 0
+
+    def run(sample):
+        tt, ut = _gpu(texture).requires_grad_(True), _gpu(uv).requires_grad_(True)
+        texels, valid = sample(tt, ut)
+        texels.backward(_gpu(grad))
+        torch.cuda.synchronize()
+        return dict(texels=_np(texels), valid=_np(valid), grad_uv=_np(ut.grad), grad_texture=_np(tt.grad))
+
+    def plain(tt, ut):
+        texels, valid = deferred.sample_texture(tt, ut, _gpu(mask), wrap)
+        _fused_node(texels, "_SampleTextureFn")
+        return texels, valid
+
+    want = run(plain)
+    assert want["valid"].any() and not want["valid"].all()
+    rng = np.random.default_rng(20)
+    for lod, lod_bias in ((None, 0.0), (rng.uniform(-3.0, 9.0, uv.shape[:-1]).astype(np.float32), 0.75)):
+        def mip(tt, ut):
+            mips = deferred.build_mipmaps(tt, levels=1)
+            assert len(mips) == 1
+            texels, valid = deferred.sample_texture_mip(mips, ut, _gpu(mask), wrap, _gpu(lod), lod_bias)
+            _fused_node(texels, "_SampleTextureMipFn")
+            return texels, valid
+
+        got = run(mip)
+        for name in ("texels", "grad_uv", "grad_texture"):
+            assert got[name].shape == want[name].shape, (name, lod_bias)
+            assert np.array_equal(_bits(got[name]), _bits(want[name])), (name, lod_bias)
+        assert got["valid"].dtype == np.bool_ and np.array_equal(got["valid"], want["valid"]), lod_bias
 
 
 def test_integer_lod_does_not_read_the_next_level():
