@@ -291,6 +291,7 @@ struct EventPair {
 #include "lighting_kernels.h"
 #include "deferred_kernels.h"
 #include "shade_lights_kernels.h"
+#include "shade_sh_kernels.h"
 #include "texture_kernels.h"
 #include "texture_mip_kernels.h"
 
@@ -1669,6 +1670,113 @@ int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, 
             positions, colors, normals, B, H, W, A, grad_pixels, route, grad_positions, grad_colors, grad_normals,
             nullptr);
     }
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- deferred shading under spherical-harmonic lighting (shade_sh_kernels.h)
+
+namespace {
+
+// the argument checks the three entry points share beyond deferred_sizes': DIRT_OK with *pixels = B * H * W
+int shade_sh_sizes(int B, int H, int W, int n_coeffs, int64_t *pixels)
+{
+    const int rc = deferred_sizes("deferred_shade_sh", B, H, W, 3, pixels);
+    if (rc) return rc;
+    if (n_coeffs != 1 && n_coeffs != 4 && n_coeffs != 9)
+        return fail(DIRT_EINVAL, "deferred_shade_sh: expects 1, 4 or 9 coefficients (bands 0, 0-1, 0-2)");
+    return DIRT_OK;
+}
+
+int64_t shade_sh_chunks(int H, int W) { return ((int64_t)H * W + kShThreads - 1) / kShThreads; }
+
+size_t shade_sh_workspace_bytes(int B, int H, int W, int n_coeffs)
+{
+    return (size_t)B * (size_t)shade_sh_chunks(H, W) * (size_t)(3 * n_coeffs) * sizeof(float);
+}
+
+// f(std::integral_constant<int, K>) for the K that n_coeffs names (checked by shade_sh_sizes)
+template <class F>
+void with_sh_coeff_count(int n_coeffs, F f)
+{
+    if (n_coeffs == 1) f(std::integral_constant<int, 1>());
+    else if (n_coeffs == 4) f(std::integral_constant<int, 4>());
+    else f(std::integral_constant<int, 9>());
+}
+
+template <int K>
+void launch_shade_sh_bwd(const float *colors, const float *normals, int B, int H, int W, const ShadeShArgs &A,
+                         const float *grad_pixels, const uint32_t *route, float *grad_colors, float *grad_normals,
+                         float *partial, hipStream_t stream)
+{
+    const dim3 grid((unsigned)shade_sh_chunks(H, W), (unsigned)std::min(B, 65535));  // (at most 8192^2 / 256 chunks)
+    if (partial)
+        shade_sh_bwd_kernel<K, true><<<grid, dim3(kShThreads), 0, stream>>>(colors, normals, B, H, W, A, grad_pixels,
+                                                                            route, grad_colors, grad_normals, partial);
+    else
+        shade_sh_bwd_kernel<K, false><<<grid, dim3(kShThreads), 0, stream>>>(colors, normals, B, H, W, A, grad_pixels,
+                                                                             route, grad_colors, grad_normals, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_deferred_shade_sh_workspace(int B, int H, int W, int n_coeffs, size_t *bytes)
+{
+    int64_t n;
+    const int rc = shade_sh_sizes(B, H, W, n_coeffs, &n);
+    if (rc) return rc;
+    if (!bytes) return fail(DIRT_EINVAL, "deferred_shade_sh: null pointer");
+    *bytes = shade_sh_workspace_bytes(B, H, W, n_coeffs);
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_sh_fwd(const float *colors, const float *normals, const uint8_t *mask, int B, int H, int W,
+                               int n_coeffs, int coeffs_per_frame, const float *coefficients, int normalize,
+                               float *pixels, uint8_t *valid, uint32_t *route, void *stream_)
+{
+    int64_t n;
+    const int rc = shade_sh_sizes(B, H, W, n_coeffs, &n);
+    if (rc || n == 0) return rc;
+    if (!colors || !normals || !coefficients || !pixels || !valid || !route)
+        return fail(DIRT_EINVAL, "deferred_shade_sh: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeShArgs A = {coefficients, coeffs_per_frame != 0, normalize != 0};
+    with_sh_coeff_count(n_coeffs, [&](auto k) {
+        shade_sh_fwd_kernel<decltype(k)::value><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+            colors, normals, mask, H, W, n, A, pixels, valid, route);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_sh_bwd(const float *colors, const float *normals, int B, int H, int W, int n_coeffs,
+                               int coeffs_per_frame, const float *coefficients, int normalize,
+                               const float *grad_pixels, const uint32_t *route, float *grad_colors,
+                               float *grad_normals, float *grad_coefficients, void *workspace,
+                               size_t workspace_bytes, void *stream_)
+{
+    int64_t n;
+    const int rc = shade_sh_sizes(B, H, W, n_coeffs, &n);
+    if (rc || n == 0 || (!grad_colors && !grad_normals && !grad_coefficients)) return rc;
+    if (!colors || !normals || !coefficients || !grad_pixels || !route)
+        return fail(DIRT_EINVAL, "deferred_shade_sh: null pointer");
+    if (grad_coefficients && (!workspace || workspace_bytes < shade_sh_workspace_bytes(B, H, W, n_coeffs)))
+        return fail(DIRT_EINVAL, "deferred_shade_sh: workspace smaller than dirt_deferred_shade_sh_workspace() "
+                                 "reports");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeShArgs A = {coefficients, coeffs_per_frame != 0, normalize != 0};
+    float *partial = grad_coefficients ? static_cast<float *>(workspace) : nullptr;
+    with_sh_coeff_count(n_coeffs, [&](auto k) {
+        launch_shade_sh_bwd<decltype(k)::value>(colors, normals, B, H, W, A, grad_pixels, route, grad_colors,
+                                                grad_normals, partial, stream);
+    });
+    if (grad_coefficients)
+        shade_sh_reduce_kernel<<<dim3((unsigned)(3 * n_coeffs)), dim3(kShThreads), 0, stream>>>(
+            partial, B, (int)shade_sh_chunks(H, W), 3 * n_coeffs, coeffs_per_frame != 0, grad_coefficients);
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }

@@ -10,6 +10,8 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
   shade_lights(positions, colors, normals, light_vectors, diffuse_colors, specular_colors, camera_position, shininess,
                ambient_color=None, point=None, double_sided=False) -> (pixels, valid): shade under up to 8 directional
                            or point lights, with gradients to the lights, the camera, the ambient colour, the shininess
+  shade_sh(colors, normals, coefficients, mask=None, normalize=False) -> (pixels, valid): the colours under 1, 4 or 9
+                           spherical-harmonic coefficients of the dilated normals, with gradients to all three
   sample_texture(texture, uv, mask=None, wrap="clamp") -> (texels, valid): bilinear texture lookup at a uv G-buffer
   build_mipmaps(texture, levels=None) -> Mipmaps: the box-filtered mip chain, packed
   sample_texture_mip(mipmaps_or_texture, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0) -> (texels, valid):
@@ -30,6 +32,11 @@ lights in one pass over the G-buffers, and parameters that need a gradient stay 
 launches: per-chunk partial sums of the per-pixel parameter terms, then their sum in a fixed order -- no float atomics,
 every gradient bit-identical from run to run.  `shade` itself is unchanged.
 
+shade_sh lights the colours with an environment instead: 9 (or 4, or 1) RGB spherical-harmonic coefficients, smooth
+in the normal and linear in the unknowns (dirt_amd/csrc/shade_sh_kernels.h, C ABI dirt_deferred_shade_sh_*; the
+statement is `_shade_sh_ops`).  One launch forward, two backward as shade_lights', the coefficients' gradient summed in
+a fixed order; it needs no positions, and its normals dilate under their own background or an explicit mask.
+
 sample_texture is the step between the two: UV -> texel, with gradients to the texture and through the uv into the
 geometry (dirt_amd/csrc/texture_kernels.h, C ABI dirt_texture_sample_*; the statement is `_sample_texture_ops`).  Its
 uv gradient is a gather in a fixed order too; its texture gradient is a scatter-add summed with float atomics (per
@@ -41,6 +48,7 @@ with the same eligibility and fallback.  The level of detail is a constant of th
 """
 import ctypes
 import os
+import struct
 
 import torch
 import torch.nn.functional as Fn
@@ -426,6 +434,148 @@ def shade_lights(positions, colors, normals, light_vectors, diffuse_colors, spec
                                                    1 if double_sided else 0), added[0])
     return _shade_lights_ops(positions, colors, normals, lights[0], lights[1], lights[2], camera_position, shininess,
                              ambient_color, point, double_sided)
+
+
+# ---- shade_sh: spherical-harmonic lighting
+
+# the basis constants, as float32 rounds them (the kernels' values, whatever the dtype of the statement)
+_SH_C = tuple(struct.unpack("f", struct.pack("f", c))[0] for c in (
+    0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396))
+_SH_COUNTS = (1, 4, 9)
+
+
+def _shade_sh_ops(colors, normals, coefficients, mask=None, normalize=False):
+    """The framework-op statement of shade_sh, each line one operation: colors, normals [H,W,3] or [B,H,W,3],
+    coefficients [K,3] or [B,K,3], mask (the normals' shape without the channels) or None."""
+    c0, c1, c2, c3, c4 = _SH_C
+    m = torch.isinf(normals).any(-1) if mask is None else mask != 0
+    nrm_d = _dilate_ops(normals, m)
+    valid = torch.isfinite(nrm_d).all(-1, keepdim=True)
+    n = torch.where(valid, nrm_d, 0.0)
+    col = torch.where(valid, colors, 0.0)
+    if normalize:
+        length = torch.linalg.norm(n, dim=-1, keepdim=True)
+        length = length + 1.e-12
+        n = n / length
+    x, y, z = n[..., 0:1], n[..., 1:2], n[..., 2:3]
+    K = coefficients.shape[-2]
+    if coefficients.dim() == 3:
+        row = lambda k: coefficients[:, k][:, None, None, :]  # noqa: E731
+    else:
+        row = lambda k: coefficients[k]  # noqa: E731
+    Y = [c0]
+    if K > 1:
+        Y += [c1 * y, c1 * z, c1 * x]
+    if K > 4:
+        xy = x * y
+        yz = y * z
+        zz = z * z
+        zz3 = 3.0 * zz
+        zz31 = zz3 - 1.0
+        xz = x * z
+        xx = x * x
+        yy = y * y
+        xxyy = xx - yy
+        Y += [c2 * xy, c2 * yz, c3 * zz31, c2 * xz, c4 * xxyy]
+    E = row(0) * Y[0]
+    for k in range(1, K):
+        term = row(k) * Y[k]
+        E = E + term
+    pixels = col * E
+    return torch.where(valid, pixels, 0.0), valid
+
+
+class _ShadeShFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colors, normals, coefficients, mask, normalize):
+        B, H, W, _ = colors.shape
+        dev = colors.device
+        pixels = torch.empty_like(colors)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        route = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        ctx.args = (coefficients.shape[-2], 1 if coefficients.dim() == 3 else 0, normalize)
+        K, per_frame, normalize = ctx.args
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_deferred_shade_sh_fwd(
+                colors.data_ptr(), normals.data_ptr(), _ptr(mask), B, H, W, K, per_frame, coefficients.data_ptr(),
+                normalize, pixels.data_ptr(), valid.data_ptr(), route.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(colors, normals, coefficients, route)
+        valid = valid.view(torch.bool)  # (the kernel writes 0 / 1)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)  # (as the shade: no zero-filled "gradient" of valid)
+        return pixels, valid
+
+    @staticmethod
+    def backward(ctx, grad_pixels, _grad_valid):
+        _no_double_backward("shade_sh")
+        if grad_pixels is None:
+            return (None,) * 5
+        colors, normals, coefficients, route = ctx.saved_tensors
+        K, per_frame, normalize = ctx.args
+        B, H, W, _ = colors.shape
+        dev = colors.device
+        grad_pixels = grad_pixels.contiguous()
+        # (NULL for the gradients nobody needs: the kernels then skip them, and without the coefficients' the partial
+        # sums and the second launch as well)
+        grads = [torch.empty_like(t) if need else None
+                 for t, need in zip((colors, normals, coefficients), ctx.needs_input_grad[:3])]
+        lib = _lib.load()
+        workspace, size = None, _lib._SZ(0)
+        if grads[2] is not None:
+            _lib.check(lib.dirt_deferred_shade_sh_workspace(B, H, W, K, ctypes.byref(size)))
+            workspace = torch.empty((max(size.value, 4),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.dirt_deferred_shade_sh_bwd(
+                colors.data_ptr(), normals.data_ptr(), B, H, W, K, per_frame, coefficients.data_ptr(), normalize,
+                grad_pixels.data_ptr(), route.data_ptr(), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]),
+                _ptr(workspace), size.value, _stream(dev)))
+        return tuple(grads) + (None, None)
+
+
+def shade_sh(colors, normals, coefficients, mask=None, normalize=False):
+    """The colour G-buffer under spherical-harmonic lighting of the normal G-buffer (colors, normals: [H,W,3] or
+    [B,H,W,3], one shape; normals over a -inf background, colors over anything).
+
+    coefficients: [K,3] shared by the frames (its gradient summed over them) or [B,K,3] one set per frame of a batched
+    call, K = 1, 4 or 9 (bands 0, 0-1, 0-2); it may require a gradient and stays on the fused path when it does.
+    mask ([H,W] or [B,H,W], nonzero = dilate here; None: the pixels where a channel of normals is +-inf, `dilate`'s
+    default): the normals are dilated there by `dilate`'s rule.  normalize=True replaces the dilated normal n by
+    u = n / (|n| + 1e-12) (diffuse_point's rule for its incident vector, subgradient 0 at n = 0); normalize=False
+    uses n raw, as diffuse_directional does.  For a valid pixel, with (x, y, z) that vector:
+
+        c0 = 0.28209479177387814   c1 = 0.4886025119029199   c2 = 1.0925484305920792
+        c3 = 0.31539156525252005   c4 = 0.5462742152960396   (as float32 rounds them)
+        Y0 = c0          Y1 = c1 y        Y2 = c1 z            Y3 = c1 x
+        Y4 = c2 (x y)    Y5 = c2 (y z)    Y6 = c3 (3 z^2 - 1)  Y7 = c2 (x z)    Y8 = c4 (x^2 - y^2)
+        E_c = coefficients[0,c] Y0;  E_c = E_c + coefficients[k,c] Y_k for k = 1 .. K-1;  pixels_c = colors_c * E_c
+
+    There is no clamp: an irradiance may go negative, and a caller who wants a clamp applies it to `pixels`.  The
+    cosine-lobe factors (pi, 2 pi / 3, pi / 4) are the caller's to fold into the coefficients.
+
+    Returns (pixels, valid): valid [..., H, W, 1] bool marks the pixels whose three dilated normal values are finite;
+    the others shade to exactly 0 and carry no gradient.  On the GPU (float32 tensors on one device) the forward is
+    one fused launch and the backward two; every gradient is bit-identical from run to run."""
+    fn = "shade_sh"
+    colors = torch.as_tensor(colors)
+    normals = torch.as_tensor(normals, dtype=colors.dtype, device=colors.device)
+    if colors.dim() not in (3, 4) or colors.shape[-1] != 3 or normals.shape != colors.shape:
+        raise ValueError("%s: colors, normals must share one shape [H, W, 3] or [B, H, W, 3]" % fn)
+    if not isinstance(coefficients, torch.Tensor):
+        coefficients = torch.as_tensor(coefficients, dtype=colors.dtype, device=colors.device)
+    if coefficients.dim() not in (2, 3) or coefficients.shape[-1] != 3:
+        raise ValueError("%s: coefficients must be [K, 3] or [B, K, 3]" % fn)
+    if coefficients.shape[-2] not in _SH_COUNTS:
+        raise ValueError("%s: %d coefficients; K must be 1, 4 or 9 (bands 0, 0-1, 0-2)" % (fn, coefficients.shape[-2]))
+    if coefficients.dim() == 3 and (colors.dim() != 4 or coefficients.shape[0] != colors.shape[0]):
+        raise ValueError("%s: per-frame coefficients need one set per frame of a [B, H, W, 3] batch" % fn)
+    mask = _checked_mask(fn, mask, normals, "normals")
+    if (_FUSED_ENABLED and _gpu_f32(colors, normals, coefficients) and
+            1 <= min(colors.shape[-3:-1]) and max(colors.shape[-3:-1]) <= _lib.MAX_DIM and
+            (mask is None or mask.device == colors.device)):
+        (cb, added), (nb, _) = _batched(colors), _batched(normals)
+        return _unbatched(_ShadeShFn.apply(cb, nb, coefficients.contiguous(), _kernel_mask(mask, nb),
+                                           1 if normalize else 0), added)
+    return _shade_sh_ops(colors, normals, coefficients, mask, normalize)
 
 
 # ---- texture sampling

@@ -80,7 +80,8 @@ extern "C" {
  * dirt_dilate_bwd, dirt_deferred_shade_fwd, dirt_deferred_shade_bwd, dirt_texture_sample_fwd,
  * dirt_texture_sample_bwd, dirt_texture_mip_layout, dirt_texture_mip_build_fwd, dirt_texture_mip_build_bwd,
  * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd, dirt_deferred_shade_lights_workspace,
- * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd) */
+ * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd, dirt_deferred_shade_sh_workspace,
+ * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -361,6 +362,44 @@ int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, 
                                    float *grad_light_vectors, float *grad_diffuse_colors, float *grad_specular_colors,
                                    float *grad_camera, float *grad_shininess, void *workspace, size_t workspace_bytes,
                                    void *stream);
+
+/* deferred_shade_sh: the colour G-buffer lit by low-order spherical harmonics of the normal G-buffer, with gradients
+ * to both G-buffers and to the coefficients.  colors, normals, pixels [B,H,W,3]; mask [B,H,W] uint8, NULL = "any
+ * channel of normals[p] is +inf or -inf" (dilate's default).  normals are dilated under mask by dilate's rule; valid
+ * [B,H,W] uint8 = the three dilated values are finite; route [B,H,W]: the normals' three codes from bit 0 in dilate's
+ * layout, valid in bit 31 (the backward needs no mask).  coefficients is a DEVICE array [n_coeffs,3] shared by the
+ * frames, or [B,n_coeffs,3] with coeffs_per_frame != 0; n_coeffs is 1, 4 or 9 (bands 0, 0-1, 0-2).  Nothing is copied
+ * from the host per call: the calls can be captured into a graph.  With normalize != 0 the dilated normal n is
+ * replaced by u = n / (|n| + 1e-12) (diffuse_point's rule), else it is used raw.  For a valid pixel, (x, y, z) that
+ * vector, float32, every step one IEEE operation, the constants the float32 roundings of
+ *   c0 = 0.28209479177387814  c1 = 0.4886025119029199  c2 = 1.0925484305920792  c3 = 0.31539156525252005
+ *   c4 = 0.5462742152960396:
+ *   Y0 = c0          Y1 = c1 y        Y2 = c1 z            Y3 = c1 x
+ *   Y4 = c2 (x y)    Y5 = c2 (y z)    Y6 = c3 (3 z^2 - 1)  Y7 = c2 (x z)    Y8 = c4 (x^2 - y^2)
+ *   E_c = coefficients[0,c] Y0;  E_c = E_c + coefficients[k,c] Y_k for k = 1 .. n_coeffs - 1 in index order
+ *   pixels_c = colors_c E_c
+ * and pixels = 0 at an invalid pixel.  There is no clamp (an irradiance may be negative), and the cosine-lobe factors
+ * (pi, 2 pi / 3, pi / 4) are the caller's to fold into the coefficients.
+ * Backward, g = grad_pixels at valid pixels and 0 elsewhere: grad_colors_c = g_c E_c; with gE_c = g_c colors_c,
+ * grad_coefficients[k,c] = the sum of gE_c Y_k over the valid pixels of the frame (per-frame form) or of all frames
+ * (shared form); the normal's adjoint g_u = sum_c gE_c sum_k coefficients[k,c] grad Y_k -- with normalize passed
+ * through J = I / d - h h^T |n| / d^2, d = |n| + 1e-12, h = n / |n| (0 at n = 0) -- is routed through the dilation by
+ * dilate's gather into grad_normals.  Each of the three may be NULL; each requested one is fully overwritten.  With
+ * grad_coefficients requested, `workspace` must hold dirt_deferred_shade_sh_workspace() bytes = B * ceil(H W / 256) *
+ * 3 n_coeffs * 4 (it needs no clearing): the first kernel stores per-chunk partial sums [B][chunks][3 n_coeffs] there
+ * -- one workgroup per 256 contiguous pixels of a frame, wave butterflies, then the four waves in order -- and a second
+ * kernel on the same stream adds the chunks of a frame and then the frames in fixed orders.  No float atomics: every
+ * gradient is bit-identical from run to run.  B == 0, or nothing requested, is DIRT_OK without a launch. */
+#define DIRT_MAX_SH_COEFFS 9
+int dirt_deferred_shade_sh_workspace(int B, int H, int W, int n_coeffs, size_t *bytes);
+int dirt_deferred_shade_sh_fwd(const float *colors, const float *normals, const uint8_t *mask, int B, int H, int W,
+                               int n_coeffs, int coeffs_per_frame, const float *coefficients, int normalize,
+                               float *pixels, uint8_t *valid, uint32_t *route, void *stream);
+int dirt_deferred_shade_sh_bwd(const float *colors, const float *normals, int B, int H, int W, int n_coeffs,
+                               int coeffs_per_frame, const float *coefficients, int normalize,
+                               const float *grad_pixels, const uint32_t *route, float *grad_colors,
+                               float *grad_normals, float *grad_coefficients, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* Deferred texturing: bilinear sampling of a texture at a uv G-buffer, and its gradients.
  * texture [texture_frames,Th,Tw,C] (texture_frames = 1: shared by the B frames, = B: one per frame), uv [B,H,W,2],
