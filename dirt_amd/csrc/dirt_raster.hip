@@ -293,6 +293,7 @@ struct EventPair {
 #include "shade_lights_kernels.h"
 #include "shade_sh_kernels.h"
 #include "texture_kernels.h"
+#include "cubemap_kernels.h"
 #include "texture_mip_kernels.h"
 
 // zero two float arrays in one launch (the backward's atomically accumulated outputs)
@@ -2066,6 +2067,88 @@ int dirt_texture_sample_mip_bwd(const float *packed, int texture_frames, int Th,
     with_each_channel_count(C, [&](auto c) {
         launch_texture_mip_bwd<decltype(c)::value>(packed, fs, Th, Tw, L, uv, mask, lod, B, H, W, g, wrap, grad_texels,
                                                    grad_packed, grad_uv, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- cube-map lookup at a direction G-buffer and its gradients (cubemap_kernels.h)
+
+namespace {
+
+int cube_sizes(int cubemap_frames, int S, int C, int B, int H, int W, SampleGrid *g)
+{
+    const char *op = "texture_sample_cube";
+    char msg[160];
+    int rc = deferred_sizes(op, B, H, W, C, &g->pixels);
+    if (!rc && (S < 1 || S > DIRT_MAX_DIM)) {
+        snprintf(msg, sizeof(msg), "%s: the faces' size must be in 1..%d", op, DIRT_MAX_DIM);
+        rc = fail(DIRT_EINVAL, msg);
+    }
+    if (!rc && B > 0 && cubemap_frames != 1 && cubemap_frames != B) {
+        snprintf(msg, sizeof(msg), "%s: cubemap_frames must be 1 or the batch size", op);
+        rc = fail(DIRT_EINVAL, msg);
+    }
+    if (!rc) rc = sample_sizes(op, 1, B, H, W, DIRT_TEXTURE_CLAMP, g);
+    if (rc) g->pixels = 0;
+    return rc;
+}
+
+template <int C>
+void launch_cubemap_fwd(const float *cubemap, int64_t frame_stride, int S, const float *directions,
+                        const uint8_t *mask, int64_t hw, int64_t n, float *texels, uint8_t *valid, hipStream_t stream)
+{
+    cubemap_sample_fwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        cubemap, frame_stride, S, directions, mask, hw, n, texels, valid);
+}
+
+template <int C>
+void launch_cubemap_bwd(const float *cubemap, int64_t frame_stride, int S, const float *directions,
+                        const uint8_t *mask, int B, int H, int W, SampleGrid g, const float *grad, float *grad_cubemap,
+                        float *grad_directions, hipStream_t stream)
+{
+    cubemap_sample_bwd_kernel<C>
+        <<<dim3((unsigned)((int64_t)B * g.tiles_y * g.tiles_x)), dim3(kLightThreads), 0, stream>>>(
+            cubemap, frame_stride, S, directions, mask, H, W, g.tiles_x, g.tiles_y, grad, grad_cubemap, grad_directions);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_texture_sample_cube_fwd(const float *cubemap, int cubemap_frames, int S, int C, const float *directions,
+                                 const uint8_t *mask, int B, int H, int W, float *texels, uint8_t *valid, void *stream_)
+{
+    SampleGrid g;
+    const int rc = cube_sizes(cubemap_frames, S, C, B, H, W, &g);
+    if (rc || g.pixels == 0) return rc;
+    if (!cubemap || !directions || !texels || !valid) return fail(DIRT_EINVAL, "texture_sample_cube: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = cubemap_frames == 1 ? 0 : (int64_t)6 * S * S * C, hw = (int64_t)H * W;
+    with_each_channel_count(C, [&](auto c) {
+        launch_cubemap_fwd<decltype(c)::value>(cubemap, fs, S, directions, mask, hw, g.pixels, texels, valid, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_texture_sample_cube_bwd(const float *cubemap, int cubemap_frames, int S, int C, const float *directions,
+                                 const uint8_t *mask, int B, int H, int W, const float *grad_texels,
+                                 float *grad_cubemap, float *grad_directions, void *stream_)
+{
+    SampleGrid g;
+    const int rc = cube_sizes(cubemap_frames, S, C, B, H, W, &g);
+    if (rc || g.pixels == 0 || (!grad_cubemap && !grad_directions)) return rc;
+    if (!cubemap || !directions || !grad_texels) return fail(DIRT_EINVAL, "texture_sample_cube: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = cubemap_frames == 1 ? 0 : (int64_t)6 * S * S * C;
+    if (grad_cubemap)
+        HIP_TRY(hipMemsetAsync(grad_cubemap, 0, (size_t)cubemap_frames * 6 * S * S * C * sizeof(float), stream));
+    with_each_channel_count(C, [&](auto c) {
+        launch_cubemap_bwd<decltype(c)::value>(cubemap, fs, S, directions, mask, B, H, W, g, grad_texels, grad_cubemap,
+                                               grad_directions, stream);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;

@@ -16,6 +16,7 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
   build_mipmaps(texture, levels=None) -> Mipmaps: the box-filtered mip chain, packed
   sample_texture_mip(mipmaps_or_texture, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0) -> (texels, valid):
                            trilinear lookup of the chain, the level chosen per pixel from the uv differences
+  sample_cubemap(cubemap, directions, mask=None) -> (texels, valid): bilinear cube-map lookup at a direction G-buffer
 
 On the GPU both run as one fused HIP launch forward and one backward (dirt_amd/csrc/deferred_kernels.h, C ABI
 dirt_dilate_* / dirt_deferred_shade_*) when their operands are float32 tensors on one GPU and the light parameters
@@ -45,6 +46,11 @@ screen tile in an LDS patch first), so it may differ in the last bits from run t
 build_mipmaps and sample_texture_mip are its minification-safe form (dirt_amd/csrc/texture_mip_kernels.h, C ABI
 dirt_texture_mip_* / dirt_texture_sample_mip_*; the statements are `_build_mipmaps_ops`, `_sample_texture_mip_ops`),
 with the same eligibility and fallback.  The level of detail is a constant of the backward: it carries no gradient.
+
+sample_cubemap looks a pixel up by direction: the specular half of an environment (a reflection vector) or a sky (the
+view ray), with gradients to the cube map's texels and through the direction into the geometry
+(dirt_amd/csrc/cubemap_kernels.h, C ABI dirt_texture_sample_cube_*; the statement is `_sample_cubemap_ops`).  A face is
+filtered as sample_texture filters a clamped texture, never across a seam; the gradients behave as sample_texture's.
 """
 import ctypes
 import os
@@ -993,3 +999,136 @@ def sample_texture_mip(mipmaps, uv, mask=None, wrap="clamp", lod=None, lod_bias=
     build_mipmaps to the texture, reaches every texel under a minified pixel's footprint.  On the GPU the uv gradient
     and build_mipmaps' backward are bit-identical from run to run; the chain's gradient is summed with float atomics."""
     return _sample_texture_mip(mipmaps, uv, mask, wrap, lod, lod_bias)[:2]
+
+
+# ---- cube-map sampling
+
+def _cube_coordinates(directions, sampled):
+    """The face rule, each line one operation: (face int64, u, v) of the pixels in `sampled`; the others take the
+    direction (1, 1, 1), so that no index and no NaN is formed from theirs.  The face choice has derivative 0."""
+    d = torch.where(sampled[..., None], directions, 1.0)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    ax, ay, az = x.abs(), y.abs(), z.abs()
+    is_x = (ax >= ay) & (ax >= az)
+    is_y = ~is_x & (ay >= az)
+    ma = torch.where(is_x, x, torch.where(is_y, y, z))
+    neg = ma < 0  # (-0.0 takes the positive face)
+    face = torch.where(is_x, 0, torch.where(is_y, 2, 4)) + neg.to(torch.int64)
+    sc = torch.where(is_x, torch.where(neg, z, -z), torch.where(is_y, x, torch.where(neg, -x, x)))
+    tc = torch.where(is_y, torch.where(neg, -z, z), -y)
+    m = ma.abs()
+    su = sc / m
+    sv = tc / m
+    u = su + 1.0
+    u = u * 0.5
+    v = sv + 1.0
+    v = v * 0.5
+    return face, u, v
+
+
+def _sample_cubemap_ops(cubemap, directions, mask=None):
+    """cubemap [6,S,S,C] or [B,6,S,S,C], directions [H,W,3] or [B,H,W,3], mask (directions' shape without the
+    channels) or None."""
+    valid = torch.isfinite(directions).all(-1) & (directions != 0).any(-1)
+    if mask is not None:
+        valid = valid & (mask != 0)
+    S = cubemap.shape[-2]
+    face, u, v = _cube_coordinates(directions, valid)
+    j0, j1, a = _texture_axis(u, S, "clamp")
+    i0, i1, b = _texture_axis(v, S, "clamp")
+    if cubemap.dim() == 5:
+        f = torch.arange(cubemap.shape[0], device=cubemap.device)[:, None, None]
+        t00, t01, t10, t11 = cubemap[f, face, i0, j0], cubemap[f, face, i0, j1], cubemap[f, face, i1, j0], \
+            cubemap[f, face, i1, j1]
+    else:
+        t00, t01, t10, t11 = cubemap[face, i0, j0], cubemap[face, i0, j1], cubemap[face, i1, j0], cubemap[face, i1, j1]
+    a, b = a[..., None], b[..., None]
+    oma, omb = 1.0 - a, 1.0 - b
+    top = t00 * oma + t01 * a
+    bot = t10 * oma + t11 * a
+    out = top * omb + bot * b
+    return torch.where(valid[..., None], out, 0.0), valid[..., None]
+
+
+class _SampleCubemapFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cubemap, directions, mask):
+        Cf, _, S, _, C = cubemap.shape
+        B, H, W, _ = directions.shape
+        dev = directions.device
+        texels = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_texture_sample_cube_fwd(cubemap.data_ptr(), Cf, S, C, directions.data_ptr(),
+                                                                _ptr(mask), B, H, W, texels.data_ptr(),
+                                                                valid.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(cubemap, directions, mask)
+        valid = valid.view(torch.bool)  # (the kernel writes 0 / 1)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)  # (as the shade: no zero-filled "gradient" of valid)
+        return texels, valid
+
+    @staticmethod
+    def backward(ctx, grad_texels, _grad_valid):
+        _no_double_backward("sample_cubemap")
+        if grad_texels is None:
+            return None, None, None
+        cubemap, directions, mask = ctx.saved_tensors
+        Cf, _, S, _, C = cubemap.shape
+        B, H, W, _ = directions.shape
+        dev = directions.device
+        grad_texels = grad_texels.contiguous()
+        # (NULL for the gradient nobody needs: the kernel then skips it; grad_cubemap is zero-filled by the call)
+        grad_cubemap = torch.empty_like(cubemap) if ctx.needs_input_grad[0] else None
+        grad_directions = torch.empty_like(directions) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_texture_sample_cube_bwd(cubemap.data_ptr(), Cf, S, C, directions.data_ptr(),
+                                                                _ptr(mask), B, H, W, grad_texels.data_ptr(),
+                                                                _ptr(grad_cubemap), _ptr(grad_directions),
+                                                                _stream(dev)))
+        return grad_cubemap, grad_directions, None
+
+
+def sample_cubemap(cubemap, directions, mask=None):
+    """Bilinear lookup of cubemap ([6,S,S,C]: shared by every frame, its gradient sums over them; or [B,6,S,S,C]: one
+    per frame) at directions ([H,W,3] or [B,H,W,3]; they need not be unit length).  The faces are square, in the order
+    +x, -x, +y, -y, +z, -z, each laid out as sample_texture's texture: top row first, texel (i,j) centred at
+    u = (j + 0.5) / S, v = (i + 0.5) / S.  With (x, y, z) a direction:
+
+        major axis: x if |x| >= |y| and |x| >= |z|, else y if |y| >= |z|, else z; ma is that component, and the face
+        is the negative one exactly when ma < 0.  (sc, tc) by the OpenGL table:
+          +x: (-z, -y)   -x: (+z, -y)   +y: (+x, +z)   -y: (+x, -z)   +z: (+x, -y)   -z: (-x, -y)
+        u = (sc / |ma| + 1) * 0.5,  v = (tc / |ma| + 1) * 0.5
+
+    and the face is filtered at (u, v) as sample_texture filters a texture with wrap="clamp".  Filtering clamps to the
+    face's edge: there is no filtering across face seams, and a caller who wants seamless lookups pads the faces.
+
+    A pixel is sampled where mask ([H,W] or [B,H,W]) is nonzero (mask=None: everywhere) and its direction's three
+    values are finite and not all zero, so a direction G-buffer rendered over -inf needs no mask, and a mask never
+    makes a zero or non-finite direction form an address.
+
+    Returns (texels, valid): valid [..., H, W, 1] bool marks the sampled pixels and carries no gradient; the others
+    give exactly 0 and carry no gradient.  The directions' gradient takes the derivative of the face choice and of
+    floor as 0, and is orthogonal to the direction (the lookup does not depend on its length); on the GPU it is
+    bit-identical from run to run, while the cube map's gradient is summed with float atomics and may differ in the
+    last bits."""
+    fn = "sample_cubemap"
+    cubemap = torch.as_tensor(cubemap)
+    directions = torch.as_tensor(directions, dtype=cubemap.dtype, device=cubemap.device)
+    if directions.dim() not in (3, 4) or directions.shape[-1] != 3:
+        raise ValueError("%s: directions must be [H, W, 3] or [B, H, W, 3]" % fn)
+    if cubemap.dim() not in (4, 5) or cubemap.shape[-4] != 6:
+        raise ValueError("%s: cubemap must be [6, S, S, C] or [B, 6, S, S, C], not %s" % (fn, tuple(cubemap.shape)))
+    if cubemap.shape[-3] != cubemap.shape[-2] or min(cubemap.shape[-2:]) < 1:
+        raise ValueError("%s: the faces must be square and non-empty, not %s" % (fn, tuple(cubemap.shape[-3:])))
+    if cubemap.dim() == 5 and (directions.dim() != 4 or cubemap.shape[0] != directions.shape[0]):
+        raise ValueError("%s: a per-frame cubemap of shape %s for directions of shape %s"
+                         % (fn, tuple(cubemap.shape), tuple(directions.shape)))
+    mask = _checked_mask(fn, mask, directions, "directions")
+    if (_FUSED_ENABLED and _gpu_f32(cubemap, directions) and 1 <= cubemap.shape[-1] <= _lib.MAX_CHANNELS and
+            cubemap.shape[-2] <= _lib.MAX_DIM and
+            1 <= min(directions.shape[-3:-1]) and max(directions.shape[-3:-1]) <= _lib.MAX_DIM and
+            (mask is None or mask.device == directions.device)):
+        (cb, _), (db, added) = _batched(cubemap, 5), _batched(directions)
+        return _unbatched(_SampleCubemapFn.apply(cb, db, _kernel_mask(mask, db)), added)
+    return _sample_cubemap_ops(cubemap, directions, mask)

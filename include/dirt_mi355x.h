@@ -81,7 +81,8 @@ extern "C" {
  * dirt_texture_sample_bwd, dirt_texture_mip_layout, dirt_texture_mip_build_fwd, dirt_texture_mip_build_bwd,
  * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd, dirt_deferred_shade_lights_workspace,
  * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd, dirt_deferred_shade_sh_workspace,
- * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd) */
+ * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd, dirt_texture_sample_cube_fwd,
+ * dirt_texture_sample_cube_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -487,6 +488,30 @@ int dirt_texture_sample_mip_fwd(const float *packed, int texture_frames, int Th,
 int dirt_texture_sample_mip_bwd(const float *packed, int texture_frames, int Th, int Tw, int C, int levels,
                                 const float *uv, const uint8_t *mask, const float *lod, int B, int H, int W, int wrap,
                                 const float *grad_texels, float *grad_packed, float *grad_uv, void *stream);
+
+/* Cube-map lookup: bilinear sampling of a cube map at a direction G-buffer, and its gradients.
+ * cubemap [cubemap_frames,6,S,S,C] (cubemap_frames = 1: shared by the B frames, = B: one per frame), faces in the order
+ * +x, -x, +y, -y, +z, -z, each laid out as a texture of dirt_texture_sample_*; directions [B,H,W,3], any length;
+ * mask [B,H,W] uint8 or NULL.  1 <= S <= DIRT_MAX_DIM, 1 <= C <= DIRT_MAX_CHANNELS.  A pixel is sampled where the mask
+ * is nonzero (NULL: everywhere) and its direction's three values are finite and not all zero; the others give texels
+ * exactly 0 and valid 0, receive gradient 0 and never form an address.  Rule (float32, every line one IEEE operation):
+ *   major axis: x if |x| >= |y| && |x| >= |z|, else y if |y| >= |z|, else z; ma = that component; the negative face
+ *   exactly when ma < 0;  (sc, tc) = +x: (-z, -y)  -x: (z, -y)  +y: (x, z)  -y: (x, -z)  +z: (x, -y)  -z: (-x, -y)
+ *   m = |ma|;  su = sc / m;  sv = tc / m;  u = su + 1;  u = u * 0.5;  v = sv + 1;  v = v * 0.5
+ * and the face's texels filtered at (u, v) by dirt_texture_sample_*'s clamp rule with Th = Tw = S: filtering clamps
+ * to the face's edge, there is none across face seams.
+ * Backward, g = grad_texels[p,:] at sampled pixels: (gu, gv) as dirt_texture_sample_bwd's grad_uv on the face, then
+ *   hu = 0.5 * gu;  hv = 0.5 * gv;  g_sc = hu / m;  g_tc = hv / m;  t = hu * su;  t2 = hv * sv;  t = t + t2
+ *   g_m = t / m;  g_m = -g_m;  g_ma = ma < 0 ? -g_m : g_m
+ * written to grad_directions [B,H,W,3] through the table's signs (fixed order, bit-identical from run to run).
+ * grad_cubemap [cubemap_frames,6,S,S,C] is zero-filled on `stream` by the call (an asynchronous memset, capturable)
+ * and receives the four-tap scatter of dirt_texture_sample_bwd into the selected face, summed with float atomics.
+ * Either gradient pointer may be NULL (not wanted); with both NULL, or B == 0, the call is a no-op. */
+int dirt_texture_sample_cube_fwd(const float *cubemap, int cubemap_frames, int S, int C, const float *directions,
+                                 const uint8_t *mask, int B, int H, int W, float *texels, uint8_t *valid, void *stream);
+int dirt_texture_sample_cube_bwd(const float *cubemap, int cubemap_frames, int S, int C, const float *directions,
+                                 const uint8_t *mask, int B, int H, int W, const float *grad_texels,
+                                 float *grad_cubemap, float *grad_directions, void *stream);
 
 /* Thread-local message for the last non-OK return on this thread. */
 const char *dirt_last_error(void);
