@@ -97,6 +97,10 @@ SIGNATURES = {
     "dirt_texture_sample_mip_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dirt_texture_sample_cube_fwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "dirt_texture_sample_cube_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "dirt_texture_sample_cube_mip_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _I, _I, _I, _I, _P, _P,
+                                              _P, _P]),
+    "dirt_texture_sample_cube_mip_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, _P,
+                                              _P, _P, _P, _P]),
     "dirt_last_error": (ctypes.c_char_p, []),
 }
 

@@ -295,6 +295,7 @@ struct EventPair {
 #include "texture_kernels.h"
 #include "cubemap_kernels.h"
 #include "texture_mip_kernels.h"
+#include "cubemap_mip_kernels.h"
 
 // zero two float arrays in one launch (the backward's atomically accumulated outputs)
 __global__ __launch_bounds__(256) void zero2_kernel(float *__restrict__ a, int64_t na, float *__restrict__ b, int64_t nb)
@@ -2149,6 +2150,105 @@ int dirt_texture_sample_cube_bwd(const float *cubemap, int cubemap_frames, int S
     with_each_channel_count(C, [&](auto c) {
         launch_cubemap_bwd<decltype(c)::value>(cubemap, fs, S, directions, mask, B, H, W, g, grad_texels, grad_cubemap,
                                                grad_directions, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- seamless mip-mapped cube-map lookup and its gradients (cubemap_mip_kernels.h)
+
+namespace {
+
+// the argument checks of the two entry points: DIRT_OK with *L the number of levels (levels <= 0: the whole chain) and
+// *texels the texels of one face's chain
+int cube_mip_sizes(int cubemap_frames, int S, int C, int levels, int B, int H, int W, int seamless, int *L,
+                   int64_t *texels, SampleGrid *g)
+{
+    const char *op = "texture_sample_cube_mip";
+    int rc = cube_sizes(cubemap_frames, S, C, B, H, W, g);
+    if (!rc) rc = mip_sizes(op, 6 * (cubemap_frames > 0 ? cubemap_frames : 0), S, S, C, levels, L, texels);
+    if (!rc && seamless != 0 && seamless != 1)
+        rc = fail(DIRT_EINVAL, "texture_sample_cube_mip: seamless must be 0 or 1");
+    if (rc) g->pixels = 0;
+    return rc;
+}
+
+template <int C>
+void launch_cubemap_mip_fwd(const float *packed, int64_t frame_stride, int64_t n_face, int S, int L,
+                            const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias, int H,
+                            int W, int64_t n, int seamless, float *texels, uint8_t *valid, float *lod,
+                            hipStream_t stream)
+{
+    cubemap_sample_mip_fwd_kernel<C><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        packed, frame_stride, n_face, S, L, directions, mask, lod_in, lod_bias, H, W, n, seamless, texels, valid, lod);
+}
+
+template <int C>
+void launch_cubemap_mip_bwd(const float *packed, int64_t frame_stride, int64_t n_face, int S, int L,
+                            const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias,
+                            const float *lod, int B, int H, int W, SampleGrid g, int seamless, const float *grad,
+                            float *grad_packed, float *grad_directions, float *grad_lod, hipStream_t stream)
+{
+    cubemap_sample_mip_bwd_kernel<C>
+        <<<dim3((unsigned)((int64_t)B * g.tiles_y * g.tiles_x)), dim3(kLightThreads), 0, stream>>>(
+            packed, frame_stride, n_face, S, L, directions, mask, lod_in, lod_bias, lod, H, W, g.tiles_x, g.tiles_y,
+            seamless, grad, grad_packed, grad_directions, grad_lod);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_texture_sample_cube_mip_fwd(const float *packed, int cubemap_frames, int S, int C, int levels,
+                                     const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias,
+                                     int B, int H, int W, int seamless, float *texels, uint8_t *valid, float *lod,
+                                     void *stream_)
+{
+    int L;
+    int64_t N;
+    SampleGrid g;
+    const int rc = cube_mip_sizes(cubemap_frames, S, C, levels, B, H, W, seamless, &L, &N, &g);
+    if (rc) return rc;
+    if (!(lod_bias - lod_bias == 0.0f)) return fail(DIRT_EINVAL, "texture_sample_cube_mip: lod_bias must be finite");
+    if (g.pixels == 0) return DIRT_OK;
+    if (!packed || !directions || !texels || !valid || !lod)
+        return fail(DIRT_EINVAL, "texture_sample_cube_mip: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = cubemap_frames == 1 ? 0 : 6 * N * C;
+    with_each_channel_count(C, [&](auto c) {
+        launch_cubemap_mip_fwd<decltype(c)::value>(packed, fs, N, S, L, directions, mask, lod_in, lod_bias, H, W,
+                                                   g.pixels, seamless, texels, valid, lod, stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_texture_sample_cube_mip_bwd(const float *packed, int cubemap_frames, int S, int C, int levels,
+                                     const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias,
+                                     const float *lod, int B, int H, int W, int seamless, const float *grad_texels,
+                                     float *grad_packed, float *grad_directions, float *grad_lod, void *stream_)
+{
+    int L;
+    int64_t N;
+    SampleGrid g;
+    const int rc = cube_mip_sizes(cubemap_frames, S, C, levels, B, H, W, seamless, &L, &N, &g);
+    if (rc) return rc;
+    if (!(lod_bias - lod_bias == 0.0f)) return fail(DIRT_EINVAL, "texture_sample_cube_mip: lod_bias must be finite");
+    if (grad_lod && !lod_in)
+        return fail(DIRT_EINVAL, "texture_sample_cube_mip: grad_lod needs the explicit lod_in it is the gradient of");
+    if (g.pixels == 0 || (!grad_packed && !grad_directions && !grad_lod)) return DIRT_OK;
+    if (!packed || !directions || !lod || !grad_texels)
+        return fail(DIRT_EINVAL, "texture_sample_cube_mip: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = cubemap_frames == 1 ? 0 : 6 * N * C;
+    if (grad_packed)
+        HIP_TRY(hipMemsetAsync(grad_packed, 0, (size_t)cubemap_frames * 6 * N * C * sizeof(float), stream));
+    with_each_channel_count(C, [&](auto c) {
+        launch_cubemap_mip_bwd<decltype(c)::value>(packed, fs, N, S, L, directions, mask, lod_in, lod_bias, lod, B, H,
+                                                   W, g, seamless, grad_texels, grad_packed, grad_directions, grad_lod,
+                                                   stream);
     });
     HIP_TRY(hipGetLastError());
     return DIRT_OK;

@@ -17,6 +17,10 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
   sample_texture_mip(mipmaps_or_texture, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0) -> (texels, valid):
                            trilinear lookup of the chain, the level chosen per pixel from the uv differences
   sample_cubemap(cubemap, directions, mask=None) -> (texels, valid): bilinear cube-map lookup at a direction G-buffer
+  build_cubemap_mipmaps(cubemap, levels=None) -> CubeMipmaps: every face's box-filtered mip chain, packed
+  sample_cubemap_mip(chain_or_cubemap, directions, mask=None, lod=None, lod_bias=0.0, seamless=True) -> (texels,
+                           valid): trilinear cube-map lookup filtered across the face seams, the level chosen per pixel
+                           or given (a roughness map), with a gradient to a given lod
 
 On the GPU both run as one fused HIP launch forward and one backward (dirt_amd/csrc/deferred_kernels.h, C ABI
 dirt_dilate_* / dirt_deferred_shade_*) when their operands are float32 tensors on one GPU and the light parameters
@@ -51,6 +55,13 @@ sample_cubemap looks a pixel up by direction: the specular half of an environmen
 view ray), with gradients to the cube map's texels and through the direction into the geometry
 (dirt_amd/csrc/cubemap_kernels.h, C ABI dirt_texture_sample_cube_*; the statement is `_sample_cubemap_ops`).  A face is
 filtered as sample_texture filters a clamped texture, never across a seam; the gradients behave as sample_texture's.
+
+build_cubemap_mipmaps and sample_cubemap_mip are the glossy step between shade_sh and sample_cubemap: the environment
+read at a level of detail that grows with the roughness (dirt_amd/csrc/cubemap_mip_kernels.h, C ABI
+dirt_texture_sample_cube_mip_*, the chain through dirt_texture_mip_build_* with six faces per frame; the statement is
+`_sample_cubemap_mip_ops`).  Every level is filtered across the face seams and the cube's corners, so that an 8 x 8 or
+1 x 1 level is no cube with hard edges.  An explicit lod receives a gradient (the difference of its two levels, at an
+integer lod the one to the right); the automatic lod, taken from the point on the unit cube, carries none.
 """
 import ctypes
 import os
@@ -825,6 +836,14 @@ def _mip_difference(uv, valid, dim):
                        torch.where(use_prev, torch.cat([zero, step], dim), torch.zeros_like(uv)))
 
 
+def _mip_lod_of_rho2(rho2, L):
+    """The rule's piecewise-linear 0.5 * log2(rho2): 0 unless rho2 >= 1, L - 1 at inf."""
+    m, e = torch.frexp(torch.where(torch.isfinite(rho2), rho2, 1.0))  # rho2 = m * 2^e, m in [0.5, 1)
+    lod = 0.5 * ((e - 1).to(rho2.dtype) + (m * 2.0 - 1.0))
+    lod = torch.where(rho2 >= 1.0, lod, 0.0)
+    return torch.where(torch.isinf(rho2), float(L - 1), lod)
+
+
 def _mip_lod_ops(uv, valid, Th, Tw, L, lod=None, lod_bias=0.0):
     """The final level of detail [...,H,W] of the rule (0 at unsampled pixels), detached: it carries no gradient."""
     uv = uv.detach()
@@ -835,11 +854,7 @@ def _mip_lod_ops(uv, valid, Th, Tw, L, lod=None, lod_bias=0.0):
             du = d[..., 0] * Tw
             dv = d[..., 1] * Th
             q.append(du * du + dv * dv)
-        rho2 = torch.fmax(q[0], q[1])  # (a NaN loses against a number)
-        m, e = torch.frexp(torch.where(torch.isfinite(rho2), rho2, 1.0))  # rho2 = m * 2^e, m in [0.5, 1)
-        lod = 0.5 * ((e - 1).to(uv.dtype) + (m * 2.0 - 1.0))
-        lod = torch.where(rho2 >= 1.0, lod, 0.0)
-        lod = torch.where(torch.isinf(rho2), float(L - 1), lod)
+        lod = _mip_lod_of_rho2(torch.fmax(q[0], q[1]), L)  # (a NaN loses against a number)
     else:
         lod = lod.detach().to(uv.dtype)
         lod = torch.where(torch.isnan(lod), 0.0, lod)
@@ -1101,7 +1116,7 @@ def sample_cubemap(cubemap, directions, mask=None):
         u = (sc / |ma| + 1) * 0.5,  v = (tc / |ma| + 1) * 0.5
 
     and the face is filtered at (u, v) as sample_texture filters a texture with wrap="clamp".  Filtering clamps to the
-    face's edge: there is no filtering across face seams, and a caller who wants seamless lookups pads the faces.
+    face's edge: there is no filtering across face seams; sample_cubemap_mip filters across them, at every level.
 
     A pixel is sampled where mask ([H,W] or [B,H,W]) is nonzero (mask=None: everywhere) and its direction's three
     values are finite and not all zero, so a direction G-buffer rendered over -inf needs no mask, and a mask never
@@ -1132,3 +1147,304 @@ def sample_cubemap(cubemap, directions, mask=None):
         (cb, _), (db, added) = _batched(cubemap, 5), _batched(directions)
         return _unbatched(_SampleCubemapFn.apply(cb, db, _kernel_mask(mask, db)), added)
     return _sample_cubemap_ops(cubemap, directions, mask)
+
+
+# ---- seamless mip-mapped cube-map sampling
+
+class CubeMipmaps:
+    """A cube map's packed mip chain: `packed` [6,N,C] (shared by the frames) or [B,6,N,C] (one per frame), face-major,
+    each face's chain as a Mipmaps packs it (N = sum_k S_k^2, S_k = S >> k while S_k is even); `dims` = ((S_0, S_0),
+    ...); `level(k)` a [..., 6, S_k, S_k, C] view of packed; len() the number of levels.  build_cubemap_mipmaps makes
+    the box-filtered chain; CubeMipmaps(packed, S, levels) wraps a chain filtered any other way (a GGX prefilter, say;
+    levels=None: the whole chain of S x S faces)."""
+
+    def __init__(self, packed, S, levels=None):
+        packed = torch.as_tensor(packed)
+        if levels is not None and (int(levels) != levels or levels < 1):
+            raise ValueError("CubeMipmaps: levels must be a positive integer or None")
+        if S < 1:
+            raise ValueError("CubeMipmaps: the faces must be non-empty")
+        dims = _mip_dims(S, S, levels)
+        if levels is not None and len(dims) != levels:
+            raise ValueError("CubeMipmaps: levels = %d, but the chain of %d x %d faces has %d"
+                             % (levels, S, S, len(dims)))
+        n = sum(h * w for h, w in dims)
+        if packed.dim() not in (3, 4) or packed.shape[-3] != 6 or packed.shape[-2] != n or packed.shape[-1] < 1 or \
+                packed.shape[0] < 1:
+            raise ValueError("CubeMipmaps: packed must be [6, N, C] or [B, 6, N, C] with N = %d for %d levels of "
+                             "%d x %d faces, not %s" % (n, len(dims), S, S, tuple(packed.shape)))
+        self.packed, self.dims = packed, tuple(dims)
+        self.offsets = tuple(sum(h * w for h, w in dims[:k]) for k in range(len(dims)))
+
+    def __len__(self):
+        return len(self.dims)
+
+    def level(self, k):
+        (h, w), o = self.dims[k], self.offsets[k]
+        return self.packed[..., o:o + h * w, :].unflatten(-2, (h, w))
+
+
+def build_cubemap_mipmaps(cubemap, levels=None):
+    """The box-filtered mip chain of cubemap ([6,S,S,C] or [B,6,S,S,C]) as a CubeMipmaps, differentiable to the cube
+    map: each face's chain is build_mipmaps' chain of that face (64 x 64 faces: seven levels, 5 x 5: one).  levels=n
+    keeps at most the first n levels.  The backward is build_mipmaps': a gather in a fixed order."""
+    fn = "build_cubemap_mipmaps"
+    cubemap = torch.as_tensor(cubemap)
+    if cubemap.dim() not in (4, 5) or cubemap.shape[-4] != 6 or min(cubemap.shape) < 1:
+        raise ValueError("%s: cubemap must be a non-empty [6, S, S, C] or [B, 6, S, S, C], not %s"
+                         % (fn, tuple(cubemap.shape)))
+    if cubemap.shape[-3] != cubemap.shape[-2]:
+        raise ValueError("%s: the faces must be square, not %s" % (fn, tuple(cubemap.shape[-3:-1])))
+    if levels is not None and (not isinstance(levels, int) or levels < 1):
+        raise ValueError("%s: levels must be a positive integer or None" % fn)
+    S = cubemap.shape[-2]
+    L = len(_mip_dims(S, S, levels))
+    faces = cubemap.reshape((-1,) + cubemap.shape[-3:])  # [Cf * 6, S, S, C]: the faces as the frames of a texture
+    if _FUSED_ENABLED and _gpu_f32(cubemap) and _mip_fused_texture(cubemap.shape):
+        packed = _BuildMipmapsFn.apply(faces.contiguous(), L)
+    else:
+        packed = _build_mipmaps_ops(faces, levels).packed
+    return CubeMipmaps(packed.reshape(cubemap.shape[:-3] + packed.shape[-2:]), S, L)
+
+
+def _cube_mip_axis(u, T):
+    """One coordinate of the tap rule, unreduced: (first tap in [-1, T - 1], weight of the second); floor has
+    derivative 0."""
+    x = u * T
+    x = x - 0.5
+    fx = torch.floor(x).detach()
+    a = x - fx
+    return torch.where(fx >= 0, torch.clamp(fx, max=T - 1), -1.0).to(torch.int64), a
+
+
+def _cube_mip_resolve(face, i, j, T):
+    """The texel that tap (i, j) of `face` resolves to at a level of T x T faces, in integers: (face', i', j', corner).
+    In range: itself.  One index out of range: folded over the edge onto the neighbouring face.  Both out of range:
+    `corner` is set (no texel exists; the indices returned are some valid ones)."""
+    oi, oj = (i < 0) | (i >= T), (j < 0) | (j >= T)
+    sc = 2 * j + 1 - T
+    tc = 2 * i + 1 - T
+    # the point by the inverse face table with major T
+    x = torch.where(face == 0, T, torch.where(face == 1, -T, torch.where(face == 5, -sc, sc)))
+    y = torch.where(face == 2, T, torch.where(face == 3, -T, -tc))
+    z = torch.where(face == 0, -sc, torch.where(face == 1, sc, torch.where(face == 2, tc, torch.where(
+        face == 3, -tc, torch.where(face == 4, T, -T)))))
+    # the fold: the old major coordinate becomes +-(T - 1), the coordinate of magnitude T + 1 the new major +-T
+    old = face >> 1
+    x = torch.where(old == 0, torch.where(x < 0, 1 - T, T - 1), x)
+    y = torch.where(old == 1, torch.where(y < 0, 1 - T, T - 1), y)
+    z = torch.where(old == 2, torch.where(z < 0, 1 - T, T - 1), z)
+    nx, ny = x.abs() > T, y.abs() > T
+    face2 = torch.where(nx, (x < 0).long(), torch.where(ny, 2 + (y < 0).long(), 4 + (z < 0).long()))
+    sc2 = torch.where(nx, torch.where(x < 0, z, -z), torch.where(ny, x, torch.where(z < 0, -x, x)))
+    tc2 = torch.where(ny, torch.where(y < 0, -z, z), -y)
+    one = oi ^ oj
+    rf = torch.where(one, face2, face)
+    ri = torch.clamp(torch.where(one, (tc2 + T - 1) >> 1, i), 0, T - 1)
+    rj = torch.clamp(torch.where(one, (sc2 + T - 1) >> 1, j), 0, T - 1)
+    return rf, ri, rj, oi & oj
+
+
+def _cube_mip_level_ops(level, face, u, v, sampled, seamless):
+    """The rule at one level ([6,T,T,C] or [B,6,T,T,C]) for the pixels in `sampled`: the four taps resolved, the corner
+    tap the mean of the other three, then `_BilinearFn` (the value is the rule's bit for bit, the gradient to u and v
+    in the kernels' difference form, and it differentiates again)."""
+    T = level.shape[-2]
+    j0, a = _cube_mip_axis(u, T)
+    i0, b = _cube_mip_axis(v, T)
+    i1, j1 = i0 + 1, j0 + 1
+    if not seamless:
+        i0, j0, i1, j1 = i0.clamp(min=0), j0.clamp(min=0), i1.clamp(max=T - 1), j1.clamp(max=T - 1)
+    vals, corner = [], []
+    for i, j in ((i0, j0), (i0, j1), (i1, j0), (i1, j1)):
+        rf, ri, rj, c = _cube_mip_resolve(face, i, j, T)
+        if level.dim() == 5:
+            f = torch.arange(level.shape[0], device=level.device)[:, None, None]
+            vals.append(level[f, rf, ri, rj])
+        else:
+            vals.append(level[rf, ri, rj])
+        corner.append(c[..., None])
+    third = 1.0 / 3.0
+    taps = []
+    for n in range(4):
+        p, q, r = [k for k in range(4) if k != n]
+        mean = vals[p] + vals[q]
+        mean = mean + vals[r]
+        mean = mean * third
+        taps.append(torch.where(corner[n], mean, vals[n]))
+    out = _BilinearFn.apply(taps[0], taps[1], taps[2], taps[3], a[..., None], b[..., None])
+    return torch.where(sampled[..., None], out, 0.0)
+
+
+class _LodBlendFn(torch.autograd.Function):
+    """The blend of two levels, out = s0 * (1 - f) + s1 * f, and out = s0 where f == 0 (s0, s1 [...,C], f [...,1]).
+    Its gradient to f is sum_c g_c * (s1_c - s0_c) at f == 0 too: the derivative to the right, so that a lod that
+    starts at an integer moves.  The backward is framework ops on the saved inputs: it differentiates again."""
+
+    @staticmethod
+    def forward(ctx, s0, s1, f):
+        ctx.save_for_backward(s0, s1, f)
+        return torch.where(f != 0, s0 * (1.0 - f) + s1 * f, s0)
+
+    @staticmethod
+    def backward(ctx, g):
+        s0, s1, f = ctx.saved_tensors
+        omf = 1.0 - f
+        return g * omf, g * f, (g * (s1 - s0)).sum(-1, keepdim=True)
+
+
+def _cube_mip_lod_ops(directions, valid, S, L, lod=None, lod_bias=0.0):
+    """The final level of detail [...,H,W] of the rule (0 at unsampled pixels).  The automatic one is detached; an
+    explicit one keeps its graph (torch.clamp passes the gradient on [0, L - 1], bounds included; a NaN gets none)."""
+    if lod is None:
+        d = torch.where(valid[..., None], directions.detach(), 1.0)
+        m = d.abs().amax(-1, keepdim=True)
+        P = d / m
+        h = 0.5 * S
+        q = []
+        for dim in (-2, -3):
+            e = _mip_difference(P, valid, dim)
+            e = e * h
+            qd = e[..., 0] * e[..., 0]
+            t = e[..., 1] * e[..., 1]
+            qd = qd + t
+            t = e[..., 2] * e[..., 2]
+            qd = qd + t
+            q.append(qd)
+        lod = _mip_lod_of_rho2(torch.fmax(q[0], q[1]), L)
+    else:
+        lod = lod.to(directions.dtype)
+        lod = torch.where(torch.isnan(lod), 0.0, lod)
+    lod = lod + lod_bias
+    lod = torch.clamp(lod, 0.0, float(L - 1))
+    return torch.where(valid, lod, 0.0)
+
+
+def _sample_cubemap_mip_ops(chain, directions, mask=None, lod=None, lod_bias=0.0, seamless=True):
+    """chain a CubeMipmaps, directions [H,W,3] or [B,H,W,3], mask and lod (directions' shape without the channels) or
+    None -> (texels, valid, the final lod)."""
+    S, L = chain.dims[0][0], len(chain)
+    valid = torch.isfinite(directions).all(-1) & (directions != 0).any(-1)
+    if mask is not None:
+        valid = valid & (mask != 0)
+    lod = _cube_mip_lod_ops(directions, valid, S, L, lod, lod_bias)
+    k0f = torch.floor(lod).detach()
+    f = (lod - k0f)[..., None]
+    k0 = k0f.to(torch.int64)
+    k1 = torch.clamp(k0 + 1, max=L - 1)
+    above = valid & (k1 != k0)
+    face, u, v = _cube_coordinates(directions, valid)
+    s0 = torch.zeros(directions.shape[:-1] + (chain.packed.shape[-1],), dtype=directions.dtype,
+                     device=directions.device)
+    s1 = s0
+    for k in range(L):  # (a level is read only by the pixels that the rule, or the lod's gradient, sends there)
+        at0, at1 = valid & (k0 == k), above & (k1 == k)
+        if not bool((at0 | at1).any()):
+            continue
+        s = _cube_mip_level_ops(chain.level(k), face, u, v, at0 | at1, seamless)
+        s0 = torch.where(at0[..., None], s, s0)
+        s1 = torch.where(at1[..., None], s, s1)
+    s1 = torch.where(above[..., None], s1, s0)  # (the top level is its own second level: no lod gradient there)
+    out = _LodBlendFn.apply(s0, s1, f)
+    return torch.where(valid[..., None], out, 0.0), valid[..., None], lod.detach()
+
+
+class _SampleCubemapMipFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, packed, directions, lod_in, mask, S, levels, lod_bias, seamless):
+        Cf, _, _, C = packed.shape
+        B, H, W, _ = directions.shape
+        dev = directions.device
+        texels = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        lod = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_texture_sample_cube_mip_fwd(
+                packed.data_ptr(), Cf, S, C, levels, directions.data_ptr(), _ptr(mask), _ptr(lod_in), lod_bias, B, H,
+                W, seamless, texels.data_ptr(), valid.data_ptr(), lod.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(packed, directions, lod_in, mask, lod)
+        ctx.args = (S, levels, lod_bias, seamless)
+        valid = valid.view(torch.bool)  # (the kernel writes 0 / 1)
+        ctx.mark_non_differentiable(valid, lod)
+        ctx.set_materialize_grads(False)  # (as sample_texture_mip: no zero-filled "gradient" of valid or the lod)
+        return texels, valid, lod
+
+    @staticmethod
+    def backward(ctx, grad_texels, _grad_valid, _grad_lod):
+        _no_double_backward("sample_cubemap_mip")
+        if grad_texels is None:
+            return (None,) * 8
+        packed, directions, lod_in, mask, lod = ctx.saved_tensors
+        S, levels, lod_bias, seamless = ctx.args
+        Cf, _, _, C = packed.shape
+        B, H, W, _ = directions.shape
+        dev = directions.device
+        grad_texels = grad_texels.contiguous()
+        # (NULL for the gradient nobody needs: the kernel then skips it; grad_packed is zero-filled by the call)
+        grad_packed = torch.empty_like(packed) if ctx.needs_input_grad[0] else None
+        grad_directions = torch.empty_like(directions) if ctx.needs_input_grad[1] else None
+        grad_lod = torch.empty_like(lod_in) if lod_in is not None and ctx.needs_input_grad[2] else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_texture_sample_cube_mip_bwd(
+                packed.data_ptr(), Cf, S, C, levels, directions.data_ptr(), _ptr(mask), _ptr(lod_in), lod_bias,
+                lod.data_ptr(), B, H, W, seamless, grad_texels.data_ptr(), _ptr(grad_packed), _ptr(grad_directions),
+                _ptr(grad_lod), _stream(dev)))
+        return (grad_packed, grad_directions, grad_lod) + (None,) * 5
+
+
+def _sample_cubemap_mip(chain, directions, mask=None, lod=None, lod_bias=0.0, seamless=True):
+    """sample_cubemap_mip with the pixels' final lod as a third result (the buffer the fused backward reads)."""
+    fn = "sample_cubemap_mip"
+    if not isinstance(chain, CubeMipmaps):
+        chain = build_cubemap_mipmaps(chain)
+    packed = chain.packed
+    directions = torch.as_tensor(directions, dtype=packed.dtype, device=packed.device)
+    if directions.dim() not in (3, 4) or directions.shape[-1] != 3:
+        raise ValueError("%s: directions must be [H, W, 3] or [B, H, W, 3]" % fn)
+    if packed.dim() == 4 and (directions.dim() != 4 or packed.shape[0] != directions.shape[0]):
+        raise ValueError("%s: a per-frame chain of shape %s for directions of shape %s"
+                         % (fn, tuple(packed.shape), tuple(directions.shape)))
+    mask = _checked_mask(fn, mask, directions, "directions")
+    if lod is not None:
+        lod = torch.as_tensor(lod, device=directions.device)
+        if lod.shape != directions.shape[:-1] or not lod.is_floating_point():
+            raise ValueError("%s: lod must be a float tensor of shape %s, not %s"
+                             % (fn, tuple(directions.shape[:-1]), tuple(lod.shape)))
+    if isinstance(lod_bias, torch.Tensor) or not float("-inf") < float(lod_bias) < float("inf"):
+        raise ValueError("%s: lod_bias must be a finite number" % fn)
+    lod_bias = float(lod_bias)
+    S, L = chain.dims[0][0], len(chain)
+    if (_FUSED_ENABLED and _gpu_f32(packed, directions) and _mip_fused_texture((S, S, packed.shape[-1])) and
+            L <= _lib.MAX_MIP_LEVELS and 1 <= min(directions.shape[-3:-1]) and
+            max(directions.shape[-3:-1]) <= _lib.MAX_DIM and (mask is None or mask.device == directions.device)):
+        (pb, _), (db, added) = _batched(packed, 4), _batched(directions)
+        lb = None if lod is None else lod.to(torch.float32).contiguous().reshape(db.shape[:-1])
+        return _unbatched(_SampleCubemapMipFn.apply(pb, db, lb, _kernel_mask(mask, db), S, L, lod_bias,
+                                                    1 if seamless else 0), added)
+    return _sample_cubemap_mip_ops(chain, directions, mask, lod, lod_bias, seamless)
+
+
+def sample_cubemap_mip(chain, directions, mask=None, lod=None, lod_bias=0.0, seamless=True):
+    """Trilinear lookup of a cube map's mip chain (a CubeMipmaps, or a plain cube map [6,S,S,C] / [B,6,S,S,C] whose
+    chain is built inside the call) at directions, with sample_cubemap's conventions for the faces, the directions,
+    the mask, the sampled pixels and the two results (texels, valid).
+
+    The level of detail is lod ([H,W] or [B,H,W], float; a NaN counts as 0) -- a roughness map scaled to levels, say --
+    or, with lod=None, taken per pixel from the differences of the point P = direction / |major component| on the
+    unit cube to the sampled neighbours (the next pixel in x and in y where there is one, else the previous one, else
+    0), scaled by S / 2 to texels: rho2 = max(|d_x|^2, |d_y|^2) and sample_texture_mip's piecewise-linear log2.  P is
+    continuous across the face seams, so the automatic lod is too.  lod_bias is added, the sum clamped to
+    [0, levels - 1], and the result is level floor(lod) blended with the next level by the fractional part (an integer
+    lod reads one level only).
+
+    With seamless=True every level is filtered across the face seams, in the manner of GL_TEXTURE_CUBE_MAP_SEAMLESS: a
+    tap past a face's edge is the texel of the neighbouring face next to it, and the one tap past a cube corner, where
+    no texel exists, is the mean of the other three.  seamless=False clamps to the face's edge at every level, which is
+    sample_cubemap's rule.
+
+    Gradients reach the chain (and through build_cubemap_mipmaps the cube map), the directions (the blend of the two
+    levels' sample_cubemap gradients, taken on the resolved taps) and an explicit lod: sum_c g_c * (s_k1 - s_k0), by
+    torch.clamp's rule zero outside [0, levels - 1], and at an integer lod the derivative to the right, so that a
+    roughness map initialised at 0 is not stuck there.  The automatic lod carries no gradient.  On the GPU the
+    directions' and the lod's gradients are bit-identical from run to run; the chain's is summed with float atomics."""
+    return _sample_cubemap_mip(chain, directions, mask, lod, lod_bias, seamless)[:2]

@@ -82,7 +82,7 @@ extern "C" {
  * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd, dirt_deferred_shade_lights_workspace,
  * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd, dirt_deferred_shade_sh_workspace,
  * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd, dirt_texture_sample_cube_fwd,
- * dirt_texture_sample_cube_bwd) */
+ * dirt_texture_sample_cube_bwd, dirt_texture_sample_cube_mip_fwd, dirt_texture_sample_cube_mip_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -512,6 +512,57 @@ int dirt_texture_sample_cube_fwd(const float *cubemap, int cubemap_frames, int S
 int dirt_texture_sample_cube_bwd(const float *cubemap, int cubemap_frames, int S, int C, const float *directions,
                                  const uint8_t *mask, int B, int H, int W, const float *grad_texels,
                                  float *grad_cubemap, float *grad_directions, void *stream);
+
+/* Seamless mip-mapped cube-map lookup: the trilinear lookup of a cube map's mip chain at a direction G-buffer, and its
+ * gradients to the chain, the directions and an explicit level of detail.
+ * packed [cubemap_frames,6,N,C]: each face's chain as dirt_texture_mip_build_fwd packs it (call that with
+ * texture_frames = 6 * cubemap_frames, Th = Tw = S; N = sum_k S_k^2, S_k = S >> k while S_k is even; `levels` as
+ * there), or a chain of that layout prefiltered any other way.  directions, mask, the sampled-pixel rule, the limits
+ * and face, ma, m, su, sv, u, v as dirt_texture_sample_cube_*.  Rule (float32, every line one IEEE operation):
+ *   lod: lod_in [B,H,W] (a NaN counts as 0), or with lod_in NULL from the point P = (x / m, y / m, z / m) on the unit
+ *     cube, which is continuous across the seams: the x-difference e = P[y,x+1] - P[y,x] if x+1 < W and that
+ *     neighbour is sampled, else P[y,x] - P[y,x-1] if x >= 1 and that neighbour is sampled, else 0; the y-difference
+ *     alike;  h = 0.5 * S;  e = e * h per component;  q = ex * ex;  t = ey * ey;  q = q + t;  t = ez * ez;  q = q + t;
+ *     rho2 = fmax(qx, qy);  then dirt_texture_sample_mip_*'s tail (lod = 0.5 * (e + (m - 1)) from rho2's bit fields,
+ *     0 unless rho2 >= 1, L-1 at inf).
+ *   lod = lod + lod_bias (finite), clamped to [0, L-1];  k0 = (int)floor(lod), f = lod - k0, k1 = min(k0+1, L-1).
+ *   taps at level k, T = S_k:  x = u * T;  x = x - 0.5;  fx = floor(x);  a = x - fx;  j0 = (int)fx;  j1 = j0 + 1 (so
+ *     j0 in [-1, T-1], j1 in [0, T]);  i0, i1, b from v alike.
+ *     seamless = 0: the four indices clamped to [0, T-1], dirt_texture_sample_cube_*'s rule at every level.
+ *     seamless = 1: tap (i, j) is resolved in integers (GL_TEXTURE_CUBE_MAP_SEAMLESS is the model).  sc = 2j + 1 - T,
+ *       tc = 2i + 1 - T, and the inverse face table with major T gives its point:
+ *         +x: (T,-tc,-sc)  -x: (-T,-tc,sc)  +y: (sc,T,tc)  -y: (sc,-T,-tc)  +z: (sc,-tc,T)  -z: (-sc,-tc,-T)
+ *       both indices in range: texel (i, j) of the pixel's face.  One out of range (one coordinate of magnitude T+1):
+ *       that coordinate becomes +-T and the major axis, the old major coordinate +-(T-1), the third stays; the face
+ *       table gives (face', sc', tc') and j' = (sc' + T - 1) / 2, i' = (tc' + T - 1) / 2, exact integers in [0, T).
+ *       Both out of range (a cube corner, at most one of the four taps): no texel exists; the tap's value is
+ *       ((t_p + t_q) + t_r) * third, third = float32(1/3), p, q, r the other three taps in the order 00, 01, 10, 11.
+ *   s_k = the bilinear rule's three lines on the four tap values;  out = s_k0 * (1 - f) + s_k1 * f;  f == 0:
+ *   out = s_k0 and level k1 is not read.
+ * texels [B,H,W,C], valid [B,H,W] uint8 (0 / 1) and lod [B,H,W] (each pixel's final lod, 0 where unsampled) are fully
+ * overwritten.
+ * Backward, with g = grad_texels[p,:] at sampled pixels; lod is the forward's buffer, lod_in and lod_bias its inputs:
+ *   grad_packed [cubemap_frames,6,N,C]: g_c * w1 * w2 * (1 - f) at the four resolved taps of k0 and g_c * w1 * w2 * f
+ *     at those of k1 (f == 0: the taps of k0 alone, weight 1); a corner tap's term times third to each of its three
+ *     source texels.  Zero-filled on `stream` by the call (an asynchronous memset, capturable), summed with float
+ *     atomics (last bits may differ between calls).
+ *   grad_directions [B,H,W,3]: per level dirt_texture_sample_bwd's grad_uv formula with T_k on the resolved tap
+ *     values (the corner tap's value is its mean; the fold, the face choice and floor have derivative 0; pass always
+ *     holds), gu = gu(k0) * (1 - f) + gu(k1) * f (f == 0: gu(k0)), then dirt_texture_sample_cube_bwd's lines.
+ *   grad_lod [B,H,W] (needs lod_in): pass ? sum_c g_c * (s_k1,c - s_k0,c) : 0, pass: lod_in is not NaN and
+ *     0 <= lod_in + lod_bias <= L-1.  At an integer lod this is the derivative to the right: level k1 is read although
+ *     the forward did not read it.  k1 == k0 gives 0.  The automatic lod carries no gradient.
+ *   grad_directions and grad_lod are gathers in a fixed order, bit-identical from run to run, zero at unsampled
+ *   pixels.  Each of the three may be NULL; with all NULL, or B == 0, no launch is made.
+ * Every argument error is a return code raised before any GPU call. */
+int dirt_texture_sample_cube_mip_fwd(const float *packed, int cubemap_frames, int S, int C, int levels,
+                                     const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias,
+                                     int B, int H, int W, int seamless, float *texels, uint8_t *valid, float *lod,
+                                     void *stream);
+int dirt_texture_sample_cube_mip_bwd(const float *packed, int cubemap_frames, int S, int C, int levels,
+                                     const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias,
+                                     const float *lod, int B, int H, int W, int seamless, const float *grad_texels,
+                                     float *grad_packed, float *grad_directions, float *grad_lod, void *stream);
 
 /* Thread-local message for the last non-OK return on this thread. */
 const char *dirt_last_error(void);
