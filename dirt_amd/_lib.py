@@ -180,6 +180,29 @@ def clip_stats(B, H, W, F, bin_capacity, scratch, scratch_bytes, stream, reset=T
     return {"cap_culled": cap.value, "clamped": clamped.value}
 
 
+LAYOUT_FIELDS = (
+    "cshift", "nctx", "ncty", "slab", "nrec",
+    "saved_fdata", "saved_cov", "saved_total",
+    "off_count", "off_flag", "off_bins", "scratch_total",
+    "kCountStride", "kParP", "kParQ", "kStatCapCulled", "kStatClamped",
+    "sizeof_Rec", "sizeof_FaceData", "kRecBboxOffset",
+    "kFusedMaxF", "kFusedMaxTiles", "kSmallPairs", "kBigCap", "kBinThreads", "kSetupSmallGrid",
+)
+
+
+@functools.lru_cache(maxsize=256)
+def debug_layout(B, H, W, F, bin_capacity=0):
+    """Debug (host only): the layout of `saved` and `scratch` for these dimensions and the constants their readers
+    need, as a dict keyed by LAYOUT_FIELDS (byte offsets, counts and word indices of the flag area)."""
+    lib = load()
+    fn = lib.dirt_debug_layout
+    fn.restype = ctypes.c_int
+    fn.argtypes = [_I, _I, _I, _I, _I64, ctypes.POINTER(ctypes.c_int64), _I]
+    out = (ctypes.c_int64 * len(LAYOUT_FIELDS))()
+    check(fn(B, H, W, F, bin_capacity, out, len(LAYOUT_FIELDS)))
+    return dict(zip(LAYOUT_FIELDS, (int(x) for x in out)))
+
+
 def stash_state(B, H, W, C, V, F, workspace, workspace_bytes, stream):
     """Debug (synchronises `stream`): {"last_missed": 1 if the last dirt_rasterise_bwd_recompute on this workspace
     recomputed, 0 if it reused the gradient stash; "magic": the stash header's magic word (0 = never written)}."""

@@ -997,6 +997,28 @@ int dirt_debug_clip_stats(int B, int H, int W, int F, int64_t bin_capacity, void
     return DIRT_OK;
 }
 
+// Debug (host only, no GPU call): the workspace layout of these dimensions and the constants a reader of `saved` and
+// `scratch` needs, as int64 words in the order below (dirt_amd/_lib.py LAYOUT_FIELDS names them); writes the
+// first n and returns EINVAL when n exceeds their number.  Not part of include/dirt_mi355x.h.
+int dirt_debug_layout(int B, int H, int W, int F, int64_t bin_capacity, int64_t *out, int n)
+{
+    Layout L;
+    int rc = make_layout(B, H, W, F, bin_capacity, L);
+    if (rc) return rc;
+    const int64_t v[] = {
+        L.cshift, L.nctx, L.ncty, (int64_t)L.slab, L.nrec,
+        (int64_t)L.saved_fdata, (int64_t)L.saved_cov, (int64_t)L.saved_total,
+        (int64_t)L.off_count, (int64_t)L.off_flag, (int64_t)L.off_bins, (int64_t)L.scratch_total,
+        kCountStride, kParP, kParQ, kStatCapCulled, kStatClamped,
+        (int64_t)sizeof(Rec), (int64_t)sizeof(FaceData), kRecBboxOffset,
+        kFusedMaxF, kFusedMaxTiles, kSmallPairs, kBigCap, kBinThreads, kSetupSmallGrid,
+    };
+    const int nv = (int)(sizeof(v) / sizeof(v[0]));
+    if (!out || n < 0 || n > nv) return fail(DIRT_EINVAL, "dirt_debug_layout: out null or n out of range");
+    for (int k = 0; k < n; ++k) out[k] = v[k];
+    return DIRT_OK;
+}
+
 // Debug: the automatic deep-cull rule of the current device (DeepAuto): launches issued with it, the generation of
 // the last launch reported deep (0 = none), and whether the next forward would take the occluder instantiation.
 // Not part of include/dirt_mi355x.h.
