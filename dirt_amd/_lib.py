@@ -101,6 +101,11 @@ SIGNATURES = {
                                               _P, _P]),
     "dirt_texture_sample_cube_mip_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, _P,
                                               _P, _P, _P, _P]),
+    "dirt_shadow_sample_workspace": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "dirt_shadow_sample_fwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, ctypes.c_float, ctypes.c_float, _P,
+                                    _P, _P]),
+    "dirt_shadow_sample_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, ctypes.c_float, ctypes.c_float, _P,
+                                    _P, _P, _P, _P, _SZ, _P]),
     "dirt_last_error": (ctypes.c_char_p, []),
 }
 

@@ -296,6 +296,7 @@ struct EventPair {
 #include "cubemap_kernels.h"
 #include "texture_mip_kernels.h"
 #include "cubemap_mip_kernels.h"
+#include "shadow_kernels.h"
 
 // zero two float arrays in one launch (the backward's atomically accumulated outputs)
 __global__ __launch_bounds__(256) void zero2_kernel(float *__restrict__ a, int64_t na, float *__restrict__ b, int64_t nb)
@@ -2272,6 +2273,110 @@ int dirt_texture_sample_cube_mip_bwd(const float *packed, int cubemap_frames, in
                                                    W, g, seamless, grad_texels, grad_packed, grad_directions, grad_lod,
                                                    stream);
     });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- shadow-map lookup at a position G-buffer and its gradients (shadow_kernels.h)
+
+namespace {
+
+// the argument checks of the three entry points: DIRT_OK with g's pixel count and tile grid
+int shadow_sizes(int map_frames, int Sh, int Sw, int B, int H, int W, float bias, float softness, SampleGrid *g)
+{
+    const char *op = "shadow_sample";
+    int rc = deferred_sizes(op, B, H, W, 1, &g->pixels);
+    if (!rc && (Sh < 1 || Sw < 1 || Sh > DIRT_MAX_DIM || Sw > DIRT_MAX_DIM)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: depth map height, width must be in 1..%d", op, DIRT_MAX_DIM);
+        rc = fail(DIRT_EINVAL, msg);
+    }
+    if (!rc && !(bias >= 0.0f && bias - bias == 0.0f && softness >= 0.0f && softness - softness == 0.0f))
+        rc = fail(DIRT_EINVAL, "shadow_sample: bias and softness must be finite and non-negative");
+    if (!rc && B > 0 && map_frames != 1 && map_frames != B)
+        rc = fail(DIRT_EINVAL, "shadow_sample: map_frames must be 1 or the batch size");
+    if (!rc) rc = sample_sizes(op, map_frames, B, H, W, DIRT_TEXTURE_CLAMP, g);
+    if (rc) g->pixels = 0;
+    return rc;
+}
+
+size_t shadow_workspace_bytes(int B, const SampleGrid &g)
+{
+    return (size_t)B * (size_t)g.tiles_y * (size_t)g.tiles_x * kShadowSums * sizeof(float);
+}
+
+ShadowArgs shadow_args(const float *light_matrix, int matrix_per_frame, float bias, float softness)
+{
+    return {light_matrix, matrix_per_frame != 0, bias, softness, softness > 0.0f ? 1.0f / softness : 0.0f};
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_shadow_sample_workspace(int B, int H, int W, size_t *bytes)
+{
+    SampleGrid g;
+    const int rc = shadow_sizes(1, 1, 1, B, H, W, 0.0f, 0.0f, &g);
+    if (rc) return rc;
+    if (!bytes) return fail(DIRT_EINVAL, "shadow_sample: null pointer");
+    *bytes = shadow_workspace_bytes(B, g);
+    return DIRT_OK;
+}
+
+int dirt_shadow_sample_fwd(const float *depth_map, int map_frames, int Sh, int Sw, const float *positions,
+                           const uint8_t *mask, int B, int H, int W, int matrix_per_frame, const float *light_matrix,
+                           float bias, float softness, float *visibility, uint8_t *valid, void *stream_)
+{
+    SampleGrid g;
+    const int rc = shadow_sizes(map_frames, Sh, Sw, B, H, W, bias, softness, &g);
+    if (rc || g.pixels == 0) return rc;
+    if (!depth_map || !positions || !light_matrix || !visibility || !valid)
+        return fail(DIRT_EINVAL, "shadow_sample: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = map_frames == 1 ? 0 : (int64_t)Sh * Sw;
+    shadow_sample_fwd_kernel<<<dim3(light_blocks(g.pixels)), dim3(kLightThreads), 0, stream>>>(
+        depth_map, fs, Sh, Sw, positions, mask, (int64_t)H * W, g.pixels,
+        shadow_args(light_matrix, matrix_per_frame, bias, softness), visibility, valid);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_shadow_sample_bwd(const float *depth_map, int map_frames, int Sh, int Sw, const float *positions,
+                           const uint8_t *mask, int B, int H, int W, int matrix_per_frame, const float *light_matrix,
+                           float bias, float softness, const float *grad_visibility, float *grad_depth_map,
+                           float *grad_positions, float *grad_light_matrix, void *workspace, size_t workspace_bytes,
+                           void *stream_)
+{
+    SampleGrid g;
+    const int rc = shadow_sizes(map_frames, Sh, Sw, B, H, W, bias, softness, &g);
+    if (rc || g.pixels == 0 || (!grad_depth_map && !grad_positions && !grad_light_matrix)) return rc;
+    if (!depth_map || !positions || !light_matrix || !grad_visibility)
+        return fail(DIRT_EINVAL, "shadow_sample: null pointer");
+    if (grad_light_matrix && (!workspace || workspace_bytes < shadow_workspace_bytes(B, g)))
+        return fail(DIRT_EINVAL, "shadow_sample: workspace smaller than dirt_shadow_sample_workspace() reports");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int64_t fs = map_frames == 1 ? 0 : (int64_t)Sh * Sw;
+    if (grad_depth_map)
+        HIP_TRY(hipMemsetAsync(grad_depth_map, 0, (size_t)map_frames * Sh * Sw * sizeof(float), stream));
+    const ShadowArgs A = shadow_args(light_matrix, matrix_per_frame, bias, softness);
+    const int64_t tiles = (int64_t)g.tiles_y * g.tiles_x;
+    const dim3 grid((unsigned)((int64_t)B * tiles));
+    float *partial = static_cast<float *>(workspace);
+    if (grad_light_matrix) {
+        shadow_sample_bwd_kernel<true><<<grid, dim3(kLightThreads), 0, stream>>>(
+            depth_map, fs, Sh, Sw, positions, mask, H, W, g.tiles_x, g.tiles_y, A, grad_visibility, grad_depth_map,
+            grad_positions, partial);
+        shadow_reduce_kernel<<<dim3(kShadowSums), dim3(kSlThreads), 0, stream>>>(partial, B, tiles,
+                                                                                 matrix_per_frame != 0,
+                                                                                 grad_light_matrix);
+    } else {
+        shadow_sample_bwd_kernel<false><<<grid, dim3(kLightThreads), 0, stream>>>(
+            depth_map, fs, Sh, Sw, positions, mask, H, W, g.tiles_x, g.tiles_y, A, grad_visibility, grad_depth_map,
+            grad_positions, nullptr);
+    }
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }

@@ -21,6 +21,9 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
   sample_cubemap_mip(chain_or_cubemap, directions, mask=None, lod=None, lod_bias=0.0, seamless=True) -> (texels,
                            valid): trilinear cube-map lookup filtered across the face seams, the level chosen per pixel
                            or given (a roughness map), with a gradient to a given lod
+  sample_shadow(depth_map, positions, light_matrix, bias=0.0, softness=0.0, mask=None) -> (visibility, valid): a
+                           light's shadow map looked up at the world-position G-buffer, 2 x 2 percentage-closer taps
+                           over a soft ramp, with gradients to the map, the positions and the light's matrix
 
 On the GPU both run as one fused HIP launch forward and one backward (dirt_amd/csrc/deferred_kernels.h, C ABI
 dirt_dilate_* / dirt_deferred_shade_*) when their operands are float32 tensors on one GPU and the light parameters
@@ -62,6 +65,14 @@ dirt_texture_sample_cube_mip_*, the chain through dirt_texture_mip_build_* with 
 `_sample_cubemap_mip_ops`).  Every level is filtered across the face seams and the cube's corners, so that an 8 x 8 or
 1 x 1 level is no cube with hard edges.  An explicit lod receives a gradient (the difference of its two levels, at an
 integer lod the one to the right); the automatic lod, taken from the point on the unit cube, carries none.
+
+sample_shadow lets a light of shade_lights be blocked (dirt_amd/csrc/shadow_kernels.h, C ABI dirt_shadow_sample_*; the
+statement is `_sample_shadow_ops`).  The light's depth map is a 1-channel `rasterise` of its clip-space z over +inf;
+the lookup projects each pixel's world position with the light's matrix, compares the four bilinear taps with its
+clip z over a ramp of width `softness`, and returns the blend: a visibility that multiplies one shade_lights call per
+shadowed light.  One launch forward; backward one launch, a workgroup per 16 x 16 screen tile -- the positions'
+gradient a gather, the depth map's a scatter-add through sample_texture's LDS patch -- and, when the matrix needs a
+gradient (it stays on the fused path), shade_lights' second launch that sums the tiles' partial sums in a fixed order.
 """
 import ctypes
 import os
@@ -1448,3 +1459,164 @@ def sample_cubemap_mip(chain, directions, mask=None, lod=None, lod_bias=0.0, sea
     roughness map initialised at 0 is not stuck there.  The automatic lod carries no gradient.  On the GPU the
     directions' and the lod's gradients are bit-identical from run to run; the chain's is summed with float atomics."""
     return _sample_cubemap_mip(chain, directions, mask, lod, lod_bias, seamless)[:2]
+
+
+# ---- shadow-map lookup
+
+def _sample_shadow_ops(depth_map, positions, light_matrix, bias=0.0, softness=0.0, mask=None):
+    """depth_map [Sh,Sw,1] or [B,Sh,Sw,1], positions [H,W,3] or [B,H,W,3], light_matrix [4,4] or [B,4,4], mask
+    (positions' shape without the channels) or None.  The rule of dirt_amd/csrc/shadow_kernels.h, each line one
+    operation in the operands' dtype."""
+    dt, dev = positions.dtype, positions.device
+    valid = torch.isfinite(positions).all(-1) if mask is None else mask != 0
+    M = light_matrix if light_matrix.dim() == 2 else light_matrix[:, None, None]
+
+    def clip(p):
+        c = ((p[..., 0:1] * M[..., 0, :] + p[..., 1:2] * M[..., 1, :]) + p[..., 2:3] * M[..., 2, :]) + M[..., 3, :]
+        return c.unbind(-1)
+
+    def coordinates(cx, cy, cw):
+        iw = 1.0 / cw
+        return (cx * iw) * 0.5 + 0.5, 0.5 - (cy * iw) * 0.5
+
+    # which pixels are inside the light's frustum is decided on the raw positions, without a graph; the
+    # differentiable pass then starts from operands made harmless wherever a pixel is not inside (an inside pixel
+    # has finite positions and cw > 0, and its values are the first pass's), so that no 0 * inf reaches a gradient
+    with torch.no_grad():
+        cx, cy, _, cw = clip(positions)
+        u, v = coordinates(cx, cy, cw)
+        inside = valid & (cw > 0) & (u >= 0) & (u <= 1) & (v >= 0) & (v <= 1)
+    cx, cy, cz, cw = clip(torch.where(inside[..., None], positions, 0.0))
+    u, v = coordinates(torch.where(inside, cx, 0.0), torch.where(inside, cy, 0.0), torch.where(inside, cw, 1.0))
+    Sh, Sw = depth_map.shape[-3], depth_map.shape[-2]
+    j0, j1, a = _texture_axis(u, Sw, "clamp")
+    i0, i1, b = _texture_axis(v, Sh, "clamp")
+    d = depth_map[..., 0]
+    if d.dim() == 3:
+        f = torch.arange(d.shape[0], device=d.device)[:, None, None]
+        taps = d[f, i0, j0], d[f, i0, j1], d[f, i1, j0], d[f, i1, j1]
+    else:
+        taps = d[i0, j0], d[i0, j1], d[i1, j0], d[i1, j1]
+    zc = cz - torch.full((), bias, dtype=dt, device=dev)
+    if softness > 0:
+        inv = torch.ones((), dtype=dt, device=dev) / torch.full((), softness, dtype=dt, device=dev)
+        s00, s01, s10, s11 = (torch.clamp((t - zc) * inv + 1.0, 0.0, 1.0) for t in taps)
+    else:
+        s00, s01, s10, s11 = ((t >= zc).to(dt) for t in taps)
+    oma, omb = 1.0 - a, 1.0 - b
+    top = s00 * oma + s01 * a
+    bot = s10 * oma + s11 * a
+    out = top * omb + bot * b
+    lit = valid.to(dt)  # (a sampled pixel outside the frustum, or behind the light, is lit)
+    return torch.where(inside, out, lit)[..., None], valid[..., None]
+
+
+class _SampleShadowFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth_map, positions, matrix, mask, bias, softness):
+        Sf, Sh, Sw, _ = depth_map.shape
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        visibility = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        ctx.args = (1 if matrix.dim() == 3 else 0, bias, softness)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_shadow_sample_fwd(
+                depth_map.data_ptr(), Sf, Sh, Sw, positions.data_ptr(), _ptr(mask), B, H, W, ctx.args[0],
+                matrix.data_ptr(), bias, softness, visibility.data_ptr(), valid.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(depth_map, positions, matrix, mask)
+        valid = valid.view(torch.bool)  # (the kernel writes 0 / 1)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)  # (as the shade: no zero-filled "gradient" of valid)
+        return visibility, valid
+
+    @staticmethod
+    def backward(ctx, grad_visibility, _grad_valid):
+        _no_double_backward("sample_shadow")
+        if grad_visibility is None:
+            return (None,) * 6
+        depth_map, positions, matrix, mask = ctx.saved_tensors
+        matrix_pf, bias, softness = ctx.args
+        Sf, Sh, Sw, _ = depth_map.shape
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        grad_visibility = grad_visibility.contiguous()
+        # (NULL for the gradients nobody needs: the kernel then skips them, and without the matrix's the partial
+        # sums and the second launch as well; grad_depth is zero-filled by the call)
+        grads = [torch.empty_like(t) if need else None
+                 for t, need in zip((depth_map, positions, matrix), ctx.needs_input_grad[:3])]
+        lib = _lib.load()
+        workspace, size = None, _lib._SZ(0)
+        if grads[2] is not None:
+            _lib.check(lib.dirt_shadow_sample_workspace(B, H, W, ctypes.byref(size)))
+            workspace = torch.empty((max(size.value, 4),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.dirt_shadow_sample_bwd(
+                depth_map.data_ptr(), Sf, Sh, Sw, positions.data_ptr(), _ptr(mask), B, H, W, matrix_pf,
+                matrix.data_ptr(), bias, softness, grad_visibility.data_ptr(), _ptr(grads[0]), _ptr(grads[1]),
+                _ptr(grads[2]), _ptr(workspace), size.value, _stream(dev)))
+        return tuple(grads) + (None, None, None)
+
+
+def _shadow_number(fn, x, name):
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= float(x) < float("inf"):
+        raise ValueError("%s: %s must be a finite Python number >= 0" % (fn, name))
+    return float(x)
+
+
+def sample_shadow(depth_map, positions, light_matrix, bias=0.0, softness=0.0, mask=None):
+    """The visibility of a light at the pixels of a world-position G-buffer, from the light's shadow map.
+
+    depth_map ([Sh,Sw,1]: shared by every frame, its gradient sums over them; or [B,Sh,Sw,1]: one per frame) is what
+    `rasterise(..., channels=1)` returns for a render from the light with vertices = [Vw,1] @ light_matrix,
+    vertex_colors = that[:, 2:3] and background = +inf: the light's clip-space z before the divide (affine in the
+    world position under orthographic and perspective matrices alike, so the rasteriser interpolates it exactly),
+    +inf where nothing was drawn.  positions ([H,W,3] or [B,H,W,3]) is the world-position G-buffer over its -inf
+    background; the op does not dilate (pass `dilate(positions)` for the silhouette ring).  light_matrix ([4,4] or
+    [B,4,4]) is in dirt_amd.matrices' row-vector convention, clip = [p,1] @ M, and may need a gradient.  bias and
+    softness are Python numbers >= 0 in clip-z units.  A pixel is sampled where mask ([H,W] or [B,H,W]) is nonzero;
+    mask=None samples the pixels whose three position channels are finite.
+
+    A sampled pixel behind the light (cw <= 0) or outside its frustum (u = cx / cw / 2 + 1/2, v = 1/2 - cy / cw / 2
+    not both in [0,1]) is lit: visibility 1, no gradient.  Inside, the four taps of sample_texture's clamp rule at
+    (u, v) are compared with zc = cz - bias, s = d >= zc (softness == 0: 2 x 2 percentage-closer filtering) or
+    s = clamp((d - zc) / softness + 1, 0, 1) (a tap is fully lit at d + bias >= cz, fully shadowed at d + bias <=
+    cz - softness), and blended bilinearly.
+
+    Returns (visibility, valid): visibility [...,H,W,1] in [0,1], exactly 0 at unsampled pixels; valid [...,H,W,1]
+    bool marks the sampled pixels and carries no gradient.  Gradients reach the depth map (through the ramp, so only
+    at softness > 0; never at a non-finite texel), the positions and the light matrix (through the ramp into cz and
+    through the bilinear weights into cx, cy and cw).  On the GPU the positions' and the matrix's gradients are
+    bit-identical from run to run (the matrix's is summed in a fixed order, without atomics); the depth map's is
+    summed with float atomics and may differ in the last bits.
+
+    Use it with one shade_lights call per shadowed light (N = 1, ambient_color=None) multiplied by that light's
+    visibility, plus one ambient call."""
+    fn = "sample_shadow"
+    positions = torch.as_tensor(positions)
+    dt, dev = positions.dtype, positions.device
+    depth_map = torch.as_tensor(depth_map, dtype=dt, device=dev)
+    if not isinstance(light_matrix, torch.Tensor):
+        light_matrix = torch.as_tensor(light_matrix, dtype=dt, device=dev)
+    if positions.dim() not in (3, 4) or positions.shape[-1] != 3:
+        raise ValueError("%s: positions must be [H, W, 3] or [B, H, W, 3]" % fn)
+    if depth_map.dim() not in (3, 4) or depth_map.shape[-1] != 1 or min(depth_map.shape[-3:]) < 1:
+        raise ValueError("%s: depth_map must be a non-empty [Sh, Sw, 1] or [B, Sh, Sw, 1]" % fn)
+    if depth_map.dim() == 4 and (positions.dim() != 4 or depth_map.shape[0] != positions.shape[0]):
+        raise ValueError("%s: a per-frame depth_map of shape %s for positions of shape %s"
+                         % (fn, tuple(depth_map.shape), tuple(positions.shape)))
+    frames = positions.shape[0] if positions.dim() == 4 else None
+    if tuple(light_matrix.shape) not in ((4, 4), (frames, 4, 4)):
+        raise ValueError("%s: light_matrix must be [4, 4] or [B, 4, 4]" % fn)
+    bias, softness = _shadow_number(fn, bias, "bias"), _shadow_number(fn, softness, "softness")
+    mask = _checked_mask(fn, mask, positions, "positions")
+    if (_FUSED_ENABLED and _gpu_f32(positions, depth_map, light_matrix) and
+            max(depth_map.shape[-3], depth_map.shape[-2]) <= _lib.MAX_DIM and
+            1 <= min(positions.shape[-3:-1]) and max(positions.shape[-3:-1]) <= _lib.MAX_DIM and
+            (mask is None or mask.device == dev)):
+        (db, _), (pb, added) = _batched(depth_map), _batched(positions)
+        return _unbatched(_SampleShadowFn.apply(db, pb, light_matrix.contiguous(), _kernel_mask(mask, pb), bias,
+                                                softness), added)
+    if light_matrix.dtype != dt or light_matrix.device != dev:
+        light_matrix = light_matrix.to(device=dev, dtype=dt)
+    return _sample_shadow_ops(depth_map, positions, light_matrix, bias, softness, mask)

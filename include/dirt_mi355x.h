@@ -82,7 +82,8 @@ extern "C" {
  * dirt_texture_sample_mip_fwd, dirt_texture_sample_mip_bwd, dirt_deferred_shade_lights_workspace,
  * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd, dirt_deferred_shade_sh_workspace,
  * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd, dirt_texture_sample_cube_fwd,
- * dirt_texture_sample_cube_bwd, dirt_texture_sample_cube_mip_fwd, dirt_texture_sample_cube_mip_bwd) */
+ * dirt_texture_sample_cube_bwd, dirt_texture_sample_cube_mip_fwd, dirt_texture_sample_cube_mip_bwd,
+ * dirt_shadow_sample_workspace, dirt_shadow_sample_fwd, dirt_shadow_sample_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -563,6 +564,42 @@ int dirt_texture_sample_cube_mip_bwd(const float *packed, int cubemap_frames, in
                                      const float *directions, const uint8_t *mask, const float *lod_in, float lod_bias,
                                      const float *lod, int B, int H, int W, int seamless, const float *grad_texels,
                                      float *grad_packed, float *grad_directions, float *grad_lod, void *stream);
+
+/* Shadow-map lookup: the visibility of a light at a world-position G-buffer, and its gradients.
+ * depth_map [map_frames,Sh,Sw] (map_frames = 1: shared by the B frames, = B: one per frame) holds the light's
+ * clip-space z before the divide, +inf where nothing was drawn; positions [B,H,W,3]; mask [B,H,W] uint8 (NULL = "the
+ * three position channels are finite"); light_matrix [4][4], or [B][4][4] with matrix_per_frame, row vectors
+ * (clip = [p,1] @ M); bias, softness finite and >= 0, in clip-z units; visibility [B,H,W]; valid [B,H,W] uint8 (0 / 1).
+ * H, W, Sh, Sw in 1..DIRT_MAX_DIM, B >= 0 (B == 0: no-op).  Rule, float32, every step one IEEE operation:
+ *   c_j = ((p0 * M[0][j] + p1 * M[1][j]) + p2 * M[2][j]) + M[3][j]  (cx, cy, cz, cw);  iw = 1 / cw
+ *   u = (cx * iw) * 0.5 + 0.5;  v = 0.5 - (cy * iw) * 0.5;  inside = cw > 0 && 0 <= u <= 1 && 0 <= v <= 1
+ * A sampled pixel that is not inside is lit (visibility 1, no gradient, no address); an inside one takes the taps and
+ * weights of dirt_texture_sample_*'s DIRT_TEXTURE_CLAMP rule on v with Sh and u with Sw, and per tap with texel d and
+ * zc = cz - bias:   softness == 0: s = d >= zc ? 1 : 0
+ *                   softness  > 0: t = (d - zc) * (1 / softness) + 1;  s = t < 0 ? 0 : (t > 1 ? 1 : t)
+ *   visibility = (s00 * (1 - a) + s01 * a) * (1 - b) + (s10 * (1 - a) + s11 * a) * b
+ * Pixels that are not sampled give exactly 0 and valid 0.  Backward, g = grad_visibility[p] at inside pixels (the
+ * float32 order is in dirt_amd/csrc/shadow_kernels.h):
+ *   grad_depth_map[tap] += g * w_tap * (1 / softness) where softness > 0, d is finite and 0 <= t <= 1: zero-filled
+ *     on `stream` by the call (an asynchronous memset, capturable), summed with float atomics (the last bits may
+ *     differ between calls); with map_frames = 1 it sums over the frames;
+ *   grad_positions [B,H,W,3] = g_c @ M[:3]^T with g_c the adjoint of the clip coordinates (through the ramp into cz,
+ *     through u and v into cx, cy and cw): fully overwritten, exactly 0 elsewhere, bit-identical from run to run;
+ *   grad_light_matrix [4][4] or [B][4][4]: M[r][j] receives the sum over the pixels of p_r * g_c[j], M[3][j] of
+ *     g_c[j] (a shared matrix over all frames in frame order).  It needs `workspace` of
+ *     dirt_shadow_sample_workspace() bytes (no clearing): the backward writes one row of 16 partial sums per 16 x 16
+ *     screen tile with plain stores and a second launch adds them in a fixed order -- bit-identical from run to run.
+ * Each of the three may be NULL; with all NULL, or B == 0, no launch is made.  Every argument error is a return code
+ * raised before any GPU call. */
+int dirt_shadow_sample_workspace(int B, int H, int W, size_t *bytes);
+int dirt_shadow_sample_fwd(const float *depth_map, int map_frames, int Sh, int Sw, const float *positions,
+                           const uint8_t *mask, int B, int H, int W, int matrix_per_frame, const float *light_matrix,
+                           float bias, float softness, float *visibility, uint8_t *valid, void *stream);
+int dirt_shadow_sample_bwd(const float *depth_map, int map_frames, int Sh, int Sw, const float *positions,
+                           const uint8_t *mask, int B, int H, int W, int matrix_per_frame, const float *light_matrix,
+                           float bias, float softness, const float *grad_visibility, float *grad_depth_map,
+                           float *grad_positions, float *grad_light_matrix, void *workspace, size_t workspace_bytes,
+                           void *stream);
 
 /* Thread-local message for the last non-OK return on this thread. */
 const char *dirt_last_error(void);
