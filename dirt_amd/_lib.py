@@ -37,6 +37,7 @@ TEXTURE_REPEAT = 1
 MAX_MIP_LEVELS = 14    # dirt_texture_mip_*: the chain of an 8192 x 8192 texture
 MAX_LIGHTS = 8         # dirt_deferred_shade_lights_*
 MAX_SH_COEFFS = 9      # dirt_deferred_shade_sh_*: 1, 4 or 9 (bands 0, 0-1, 0-2)
+PBR_MIN_ROUGHNESS = 0.04500000178813934  # dirt_deferred_shade_pbr_*: DIRT_PBR_MIN_ROUGHNESS (0.045f) as a double
 BWD_ACCUMULATE = 1    # dirt_rasterise_bwd / dirt_rasterise_bwd_recompute flags
 BWD_SCRATCH_CLEAN = 2  # dirt_rasterise_bwd_recompute: the workspace's bin counters are clean
 
@@ -86,6 +87,11 @@ SIGNATURES = {
     "dirt_deferred_shade_sh_workspace": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "dirt_deferred_shade_sh_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "dirt_deferred_shade_sh_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dirt_deferred_shade_pbr_workspace": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "dirt_deferred_shade_pbr_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _U, _I, _P, _P, _I, _P, _P, _P, _P,
+                                         _P]),
+    "dirt_deferred_shade_pbr_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _U, _I, _P, _P, _I, _P, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dirt_texture_sample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dirt_texture_sample_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dirt_texture_mip_layout": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_longlong),

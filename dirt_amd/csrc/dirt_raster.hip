@@ -291,6 +291,7 @@ struct EventPair {
 #include "lighting_kernels.h"
 #include "deferred_kernels.h"
 #include "shade_lights_kernels.h"
+#include "shade_pbr_kernels.h"
 #include "shade_sh_kernels.h"
 #include "texture_kernels.h"
 #include "cubemap_kernels.h"
@@ -1694,6 +1695,148 @@ int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, 
         shade_lights_bwd_kernel<false><<<grid, dim3(kSlThreads), 0, stream>>>(
             positions, colors, normals, B, H, W, A, grad_pixels, route, grad_positions, grad_colors, grad_normals,
             nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- metallic-roughness deferred shading with gradients to everything (shade_pbr_kernels.h)
+
+namespace {
+
+// the argument checks the three entry points share beyond deferred_sizes': DIRT_OK with *pixels = B * H * W
+int shade_pbr_sizes(int B, int H, int W, int n_lights, unsigned point_mask, int64_t *pixels)
+{
+    const int rc = deferred_sizes("deferred_shade_pbr", B, H, W, 3, pixels);
+    if (rc) return rc;
+    if (n_lights < 0 || n_lights > DIRT_MAX_LIGHTS) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "deferred_shade_pbr: expects 0 <= lights <= %d", DIRT_MAX_LIGHTS);
+        return fail(DIRT_EINVAL, msg);
+    }
+    if (point_mask >> n_lights) return fail(DIRT_EINVAL, "deferred_shade_pbr: point_mask has bits past the lights");
+    return DIRT_OK;
+}
+
+ShadePbrArgs shade_pbr_args(const float *ambient_color, int n_lights, unsigned point_mask, int lights_per_frame,
+                            const float *light_vectors, const float *light_colors, int camera_per_frame,
+                            const float *camera_position)
+{
+    return {ambient_color, light_vectors, light_colors, camera_position, n_lights, point_mask, lights_per_frame != 0,
+            camera_per_frame != 0};
+}
+
+int64_t shade_pbr_chunks(int H, int W) { return ((int64_t)H * W + kSlThreads - 1) / kSlThreads; }
+
+size_t shade_pbr_workspace_bytes(int B, int H, int W, int n_lights)
+{
+    return (size_t)B * (size_t)shade_pbr_chunks(H, W) * (size_t)(kPbrFixedSums + kPbrSumsPerLight * n_lights) *
+           sizeof(float);
+}
+
+void launch_shade_pbr_fwd(const float *positions, const float *colors, const float *normals, const float *material,
+                          const float *visibility, int H, int W, int64_t n, const ShadePbrArgs &A, float *pixels,
+                          uint8_t *valid, uint32_t *route, hipStream_t stream)
+{
+    shade_pbr_fwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+        positions, colors, normals, material, visibility, H, W, n, A, pixels, valid, route);
+}
+
+template <bool kParams>
+void launch_shade_pbr_bwd(const float *positions, const float *colors, const float *normals, const float *material,
+                          const float *visibility, int B, int H, int W, const ShadePbrArgs &A, const float *grad_pixels,
+                          const uint32_t *route, float *grad_positions, float *grad_colors, float *grad_normals,
+                          float *grad_material, float *grad_visibility, float *partial, hipStream_t stream)
+{
+    const dim3 grid((unsigned)shade_pbr_chunks(H, W), (unsigned)std::min(B, 65535));  // (at most 8192^2 / 256 chunks)
+    shade_pbr_bwd_kernel<kParams><<<grid, dim3(kSlThreads), 0, stream>>>(
+        positions, colors, normals, material, visibility, B, H, W, A, grad_pixels, route, grad_positions, grad_colors,
+        grad_normals, grad_material, grad_visibility, partial);
+}
+
+void launch_shade_pbr_reduce(const float *partial, int B, int chunks, int n_lights, int lights_per_frame,
+                             int camera_per_frame, const PbrParamGrads &G, hipStream_t stream)
+{
+    shade_pbr_reduce_kernel<<<dim3((unsigned)(kPbrFixedSums + kPbrSumsPerLight * n_lights)), dim3(kSlThreads), 0,
+                              stream>>>(partial, B, chunks, n_lights, lights_per_frame != 0, camera_per_frame != 0, G);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_deferred_shade_pbr_workspace(int B, int H, int W, int n_lights, size_t *bytes)
+{
+    int64_t n;
+    const int rc = shade_pbr_sizes(B, H, W, n_lights, 0u, &n);
+    if (rc) return rc;
+    if (!bytes) return fail(DIRT_EINVAL, "deferred_shade_pbr: null pointer");
+    *bytes = shade_pbr_workspace_bytes(B, H, W, n_lights);
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_pbr_fwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *visibility, int B, int H, int W,
+                                const float *ambient_color, int n_lights, unsigned point_mask, int lights_per_frame,
+                                const float *light_vectors, const float *light_colors, int camera_per_frame,
+                                const float *camera_position, float *pixels, uint8_t *valid, uint32_t *route,
+                                void *stream_)
+{
+    int64_t n;
+    const int rc = shade_pbr_sizes(B, H, W, n_lights, point_mask, &n);
+    if (rc || n == 0) return rc;
+    if (!positions || !colors || !normals || !material || !pixels || !valid || !route ||
+        (n_lights > 0 && (!light_vectors || !light_colors || !camera_position)))
+        return fail(DIRT_EINVAL, "deferred_shade_pbr: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadePbrArgs A = shade_pbr_args(ambient_color, n_lights, point_mask, lights_per_frame, light_vectors,
+                                          light_colors, camera_per_frame, camera_position);
+    launch_shade_pbr_fwd(positions, colors, normals, material, visibility, H, W, n, A, pixels, valid, route, stream);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_pbr_bwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *visibility, int B, int H, int W,
+                                const float *ambient_color, int n_lights, unsigned point_mask, int lights_per_frame,
+                                const float *light_vectors, const float *light_colors, int camera_per_frame,
+                                const float *camera_position, const float *grad_pixels, const uint32_t *route,
+                                float *grad_positions, float *grad_colors, float *grad_normals, float *grad_material,
+                                float *grad_visibility, float *grad_ambient, float *grad_light_vectors,
+                                float *grad_light_colors, float *grad_camera, void *workspace, size_t workspace_bytes,
+                                void *stream_)
+{
+    int64_t n;
+    const int rc = shade_pbr_sizes(B, H, W, n_lights, point_mask, &n);
+    if (rc || n == 0) return rc;
+    if (n_lights == 0) grad_light_vectors = grad_light_colors = grad_visibility = nullptr;  // (empty arrays)
+    const bool want_params = grad_ambient || grad_light_vectors || grad_light_colors || grad_camera;
+    if (!want_params && !grad_positions && !grad_colors && !grad_normals && !grad_material && !grad_visibility)
+        return DIRT_OK;
+    if (!positions || !colors || !normals || !material || !grad_pixels || !route ||
+        (n_lights > 0 && (!light_vectors || !light_colors || !camera_position)))
+        return fail(DIRT_EINVAL, "deferred_shade_pbr: null pointer");
+    if (want_params && (!workspace || workspace_bytes < shade_pbr_workspace_bytes(B, H, W, n_lights)))
+        return fail(DIRT_EINVAL, "deferred_shade_pbr: workspace smaller than "
+                                 "dirt_deferred_shade_pbr_workspace() reports");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadePbrArgs A = shade_pbr_args(ambient_color, n_lights, point_mask, lights_per_frame, light_vectors,
+                                          light_colors, camera_per_frame, camera_position);
+    float *partial = static_cast<float *>(workspace);
+    if (want_params) {
+        launch_shade_pbr_bwd<true>(positions, colors, normals, material, visibility, B, H, W, A, grad_pixels, route,
+                                   grad_positions, grad_colors, grad_normals, grad_material, grad_visibility, partial,
+                                   stream);
+        // (the camera without lights receives exact zeros from the empty sums)
+        const PbrParamGrads G = {grad_ambient, grad_light_vectors, grad_light_colors, grad_camera};
+        launch_shade_pbr_reduce(partial, B, (int)shade_pbr_chunks(H, W), n_lights, lights_per_frame,
+                                camera_per_frame, G, stream);
+    } else {
+        launch_shade_pbr_bwd<false>(positions, colors, normals, material, visibility, B, H, W, A, grad_pixels, route,
+                                    grad_positions, grad_colors, grad_normals, grad_material, grad_visibility, nullptr,
+                                    stream);
     }
     HIP_TRY(hipGetLastError());
     return DIRT_OK;

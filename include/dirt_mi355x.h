@@ -83,7 +83,8 @@ extern "C" {
  * dirt_deferred_shade_lights_fwd, dirt_deferred_shade_lights_bwd, dirt_deferred_shade_sh_workspace,
  * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd, dirt_texture_sample_cube_fwd,
  * dirt_texture_sample_cube_bwd, dirt_texture_sample_cube_mip_fwd, dirt_texture_sample_cube_mip_bwd,
- * dirt_shadow_sample_workspace, dirt_shadow_sample_fwd, dirt_shadow_sample_bwd) */
+ * dirt_shadow_sample_workspace, dirt_shadow_sample_fwd, dirt_shadow_sample_bwd, dirt_deferred_shade_pbr_workspace,
+ * dirt_deferred_shade_pbr_fwd, dirt_deferred_shade_pbr_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -364,6 +365,49 @@ int dirt_deferred_shade_lights_bwd(const float *positions, const float *colors, 
                                    float *grad_light_vectors, float *grad_diffuse_colors, float *grad_specular_colors,
                                    float *grad_camera, float *grad_shininess, void *workspace, size_t workspace_bytes,
                                    void *stream);
+
+/* deferred_shade_pbr: the metallic-roughness model (Lambert plus a GGX microfacet lobe) under n_lights lights
+ * (0..DIRT_MAX_LIGHTS; 0 = ambient only) with a per-pixel, per-light visibility, and gradients to every input.
+ * Dilation of positions and normals, valid and the route word are deferred_shade's; colors (the base colour), material
+ * [B,H,W,2] (perceptual roughness, metallic) and visibility [B,H,W,n_lights] (NULL = ones) are read at the pixel
+ * itself.  The light arrays, the camera, the ambient colour and point_mask are deferred_shade_lights': DEVICE arrays
+ * [n_lights,3] or [B,n_lights,3], [3] or [B,3], 3 floats or NULL; a directional light's row is its direction of
+ * travel, a point light's row its position.  For a valid pixel with dilated position p, dilated normal n_d, colour c,
+ * u(x) = x / (|x| + 1e-12):
+ *   n = u(n_d)  v = u(camera - p)  l = u(-direction) or u(position - p)  h = u(l + v)
+ *   r = clamp(material_0, DIRT_PBR_MIN_ROUGHNESS, 1)  m = clamp(material_1, 0, 1)  alpha = r r  k = alpha / 2
+ *   nl = n . l  nv = max(n . v, 0)  nh = n . h  vh = clamp(v . h, 0, 1)
+ *   t = |n x h|^2 + (nh alpha)^2   D = t > 0 ? alpha^2 / (pi t^2) : 0   V = 1 / (4 (nl (1 - k) + k) (nv (1 - k) + k))
+ *   F0 = 0.04 + (c - 0.04) m   F = F0 + (1 - F0) (1 - vh)^5
+ *   term_i = nl > 0 ? visibility_i (light_color_i nl) ((1 - F) (1 - m) c / pi + D V F) : 0   (no attenuation)
+ *   pixels = term_0 + term_1 + ... + c * ambient_color, 0 at an invalid pixel.
+ * Backward: grad_positions / grad_normals are gathers through the dilation route as deferred_shade_bwd's; grad_colors,
+ * grad_material, grad_visibility receive their own pixel's terms (every clamp with torch.clamp's derivative, the two
+ * selects with none on their zero side); grad_ambient [3], grad_light_vectors, grad_light_colors, grad_camera (shaped
+ * as their parameters) receive the sums of the per-pixel terms over the valid pixels of a frame (per-frame parameters)
+ * or of all frames (shared ones).  Each of the nine may be NULL; each requested one is fully overwritten.  With a
+ * parameter gradient requested, `workspace` must hold dirt_deferred_shade_pbr_workspace() bytes = B * ceil(H W / 256)
+ * * (6 + 6 n_lights) * 4 (it needs no clearing): the first kernel stores per-chunk partial sums there -- one workgroup
+ * per 256 contiguous pixels of a frame, wave butterflies, then the four waves in order -- and a second kernel on the
+ * same stream adds the chunks of a frame and then the frames in fixed orders.  No float atomics: every gradient is
+ * bit-identical from run to run.  B == 0, or nothing requested, is DIRT_OK without a launch. */
+#define DIRT_PBR_MIN_ROUGHNESS 0.045f
+int dirt_deferred_shade_pbr_workspace(int B, int H, int W, int n_lights, size_t *bytes);
+int dirt_deferred_shade_pbr_fwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *visibility, int B, int H, int W,
+                                const float *ambient_color, int n_lights, unsigned point_mask, int lights_per_frame,
+                                const float *light_vectors, const float *light_colors, int camera_per_frame,
+                                const float *camera_position, float *pixels, uint8_t *valid, uint32_t *route,
+                                void *stream);
+int dirt_deferred_shade_pbr_bwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *visibility, int B, int H, int W,
+                                const float *ambient_color, int n_lights, unsigned point_mask, int lights_per_frame,
+                                const float *light_vectors, const float *light_colors, int camera_per_frame,
+                                const float *camera_position, const float *grad_pixels, const uint32_t *route,
+                                float *grad_positions, float *grad_colors, float *grad_normals, float *grad_material,
+                                float *grad_visibility, float *grad_ambient, float *grad_light_vectors,
+                                float *grad_light_colors, float *grad_camera, void *workspace, size_t workspace_bytes,
+                                void *stream);
 
 /* deferred_shade_sh: the colour G-buffer lit by low-order spherical harmonics of the normal G-buffer, with gradients
  * to both G-buffers and to the coefficients.  colors, normals, pixels [B,H,W,3]; mask [B,H,W] uint8, NULL = "any
