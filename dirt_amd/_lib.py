@@ -92,6 +92,13 @@ SIGNATURES = {
                                          _P]),
     "dirt_deferred_shade_pbr_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _U, _I, _P, _P, _I, _P, _P, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dirt_deferred_reflect_view_workspace": (_I, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "dirt_deferred_reflect_view_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dirt_deferred_reflect_view_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dirt_deferred_shade_env_workspace": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "dirt_deferred_shade_env_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "dirt_deferred_shade_env_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dirt_texture_sample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dirt_texture_sample_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dirt_texture_mip_layout": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_longlong),

@@ -293,6 +293,7 @@ struct EventPair {
 #include "shade_lights_kernels.h"
 #include "shade_pbr_kernels.h"
 #include "shade_sh_kernels.h"
+#include "shade_env_kernels.h"
 #include "texture_kernels.h"
 #include "cubemap_kernels.h"
 #include "texture_mip_kernels.h"
@@ -1945,6 +1946,191 @@ int dirt_deferred_shade_sh_bwd(const float *colors, const float *normals, int B,
     if (grad_coefficients)
         shade_sh_reduce_kernel<<<dim3((unsigned)(3 * n_coeffs)), dim3(kShThreads), 0, stream>>>(
             partial, B, (int)shade_sh_chunks(H, W), 3 * n_coeffs, coeffs_per_frame != 0, grad_coefficients);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+}  // extern "C"
+
+// ---- image-based lighting: the reflection vector and the split-sum combination (shade_env_kernels.h)
+
+namespace {
+
+// the argument checks the entry points share beyond deferred_sizes': DIRT_OK with *pixels = B * H * W
+int shade_env_sizes(int B, int H, int W, int n_coeffs, int64_t *pixels)
+{
+    const int rc = deferred_sizes("deferred_shade_env", B, H, W, 3, pixels);
+    if (rc) return rc;
+    if (n_coeffs != 1 && n_coeffs != 4 && n_coeffs != 9)
+        return fail(DIRT_EINVAL, "deferred_shade_env: expects 1, 4 or 9 coefficients (bands 0, 0-1, 0-2)");
+    return DIRT_OK;
+}
+
+// both ops' first backward kernel owns kSlThreads pixels a workgroup; a partial row holds `sums` floats
+int64_t env_chunks(int H, int W) { return ((int64_t)H * W + kSlThreads - 1) / kSlThreads; }
+
+size_t env_workspace_bytes(int B, int H, int W, int sums)
+{
+    return (size_t)B * (size_t)env_chunks(H, W) * (size_t)sums * sizeof(float);
+}
+
+dim3 env_bwd_grid(int B, int H, int W)
+{
+    return dim3((unsigned)env_chunks(H, W), (unsigned)std::min(B, 65535));  // (at most 8192^2 / 256 chunks)
+}
+
+void launch_env_reduce(const float *partial, int B, int H, int W, int sums, int camera_per_frame, int coeffs_per_frame,
+                       const EnvParamGrads &G, hipStream_t stream)
+{
+    shade_env_reduce_kernel<<<dim3((unsigned)sums), dim3(kSlThreads), 0, stream>>>(
+        partial, B, (int)env_chunks(H, W), sums, camera_per_frame != 0, coeffs_per_frame != 0, G);
+}
+
+template <int K>
+void launch_shade_env_bwd(const float *positions, const float *colors, const float *normals, const float *material,
+                          const float *radiance, const float *occlusion, int B, int H, int W, const ShadeEnvArgs &A,
+                          const float *grad_pixels, const uint32_t *route, float *grad_positions, float *grad_colors,
+                          float *grad_normals, float *grad_material, float *grad_radiance, float *grad_occlusion,
+                          float *partial, hipStream_t stream)
+{
+    const dim3 grid = env_bwd_grid(B, H, W);
+    if (partial)
+        shade_env_bwd_kernel<K, true><<<grid, dim3(kSlThreads), 0, stream>>>(
+            positions, colors, normals, material, radiance, occlusion, B, H, W, A, grad_pixels, route, grad_positions,
+            grad_colors, grad_normals, grad_material, grad_radiance, grad_occlusion, partial);
+    else
+        shade_env_bwd_kernel<K, false><<<grid, dim3(kSlThreads), 0, stream>>>(
+            positions, colors, normals, material, radiance, occlusion, B, H, W, A, grad_pixels, route, grad_positions,
+            grad_colors, grad_normals, grad_material, grad_radiance, grad_occlusion, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dirt_deferred_reflect_view_workspace(int B, int H, int W, size_t *bytes)
+{
+    int64_t n;
+    const int rc = deferred_sizes("deferred_reflect_view", B, H, W, 3, &n);
+    if (rc) return rc;
+    if (!bytes) return fail(DIRT_EINVAL, "deferred_reflect_view: null pointer");
+    *bytes = env_workspace_bytes(B, H, W, kEnvCamSums);
+    return DIRT_OK;
+}
+
+int dirt_deferred_reflect_view_fwd(const float *positions, const float *normals, int B, int H, int W,
+                                   int camera_per_frame, const float *camera_position, float *directions,
+                                   uint8_t *valid, uint32_t *route, void *stream_)
+{
+    int64_t n;
+    const int rc = deferred_sizes("deferred_reflect_view", B, H, W, 3, &n);
+    if (rc || n == 0) return rc;
+    if (!positions || !normals || !camera_position || !directions || !valid || !route)
+        return fail(DIRT_EINVAL, "deferred_reflect_view: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeEnvArgs A = {camera_position, camera_per_frame != 0, {nullptr, 0, 1}};
+    reflect_view_fwd_kernel<<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(positions, normals, H, W, n, A,
+                                                                                      directions, valid, route);
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_reflect_view_bwd(const float *positions, const float *normals, int B, int H, int W,
+                                   int camera_per_frame, const float *camera_position, const float *grad_directions,
+                                   const uint32_t *route, float *grad_positions, float *grad_normals,
+                                   float *grad_camera, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    int64_t n;
+    const int rc = deferred_sizes("deferred_reflect_view", B, H, W, 3, &n);
+    if (rc || n == 0 || (!grad_positions && !grad_normals && !grad_camera)) return rc;
+    if (!positions || !normals || !camera_position || !grad_directions || !route)
+        return fail(DIRT_EINVAL, "deferred_reflect_view: null pointer");
+    if (grad_camera && (!workspace || workspace_bytes < env_workspace_bytes(B, H, W, kEnvCamSums)))
+        return fail(DIRT_EINVAL, "deferred_reflect_view: workspace smaller than "
+                                 "dirt_deferred_reflect_view_workspace() reports");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeEnvArgs A = {camera_position, camera_per_frame != 0, {nullptr, 0, 1}};
+    const dim3 grid = env_bwd_grid(B, H, W);
+    if (grad_camera) {
+        float *partial = static_cast<float *>(workspace);
+        reflect_view_bwd_kernel<true><<<grid, dim3(kSlThreads), 0, stream>>>(
+            positions, normals, B, H, W, A, grad_directions, route, grad_positions, grad_normals, partial);
+        launch_env_reduce(partial, B, H, W, kEnvCamSums, camera_per_frame, 0, {grad_camera, nullptr}, stream);
+    } else {
+        reflect_view_bwd_kernel<false><<<grid, dim3(kSlThreads), 0, stream>>>(
+            positions, normals, B, H, W, A, grad_directions, route, grad_positions, grad_normals, nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_env_workspace(int B, int H, int W, int n_coeffs, size_t *bytes)
+{
+    int64_t n;
+    const int rc = shade_env_sizes(B, H, W, n_coeffs, &n);
+    if (rc) return rc;
+    if (!bytes) return fail(DIRT_EINVAL, "deferred_shade_env: null pointer");
+    *bytes = env_workspace_bytes(B, H, W, kEnvCamSums + 3 * n_coeffs);
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_env_fwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *radiance, const float *occlusion, int B, int H,
+                                int W, int n_coeffs, int coeffs_per_frame, const float *coefficients,
+                                int camera_per_frame, const float *camera_position, float *pixels, uint8_t *valid,
+                                uint32_t *route, void *stream_)
+{
+    int64_t n;
+    const int rc = shade_env_sizes(B, H, W, n_coeffs, &n);
+    if (rc || n == 0) return rc;
+    if (!positions || !colors || !normals || !material || !radiance || !coefficients || !camera_position || !pixels ||
+        !valid || !route)
+        return fail(DIRT_EINVAL, "deferred_shade_env: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeEnvArgs A = {camera_position, camera_per_frame != 0, {coefficients, coeffs_per_frame != 0, 1}};
+    with_sh_coeff_count(n_coeffs, [&](auto k) {
+        shade_env_fwd_kernel<decltype(k)::value><<<dim3(light_blocks(n)), dim3(kLightThreads), 0, stream>>>(
+            positions, colors, normals, material, radiance, occlusion, H, W, n, A, pixels, valid, route);
+    });
+    HIP_TRY(hipGetLastError());
+    return DIRT_OK;
+}
+
+int dirt_deferred_shade_env_bwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *radiance, const float *occlusion, int B, int H,
+                                int W, int n_coeffs, int coeffs_per_frame, const float *coefficients,
+                                int camera_per_frame, const float *camera_position, const float *grad_pixels,
+                                const uint32_t *route, float *grad_positions, float *grad_colors, float *grad_normals,
+                                float *grad_material, float *grad_radiance, float *grad_occlusion,
+                                float *grad_coefficients, float *grad_camera, void *workspace, size_t workspace_bytes,
+                                void *stream_)
+{
+    int64_t n;
+    const int rc = shade_env_sizes(B, H, W, n_coeffs, &n);
+    if (rc || n == 0) return rc;
+    if (!occlusion) grad_occlusion = nullptr;  // (ones: nothing to receive it)
+    const bool want_params = grad_coefficients || grad_camera;
+    if (!want_params && !grad_positions && !grad_colors && !grad_normals && !grad_material && !grad_radiance &&
+        !grad_occlusion)
+        return DIRT_OK;
+    if (!positions || !colors || !normals || !material || !radiance || !coefficients || !camera_position ||
+        !grad_pixels || !route)
+        return fail(DIRT_EINVAL, "deferred_shade_env: null pointer");
+    const int sums = kEnvCamSums + 3 * n_coeffs;
+    if (want_params && (!workspace || workspace_bytes < env_workspace_bytes(B, H, W, sums)))
+        return fail(DIRT_EINVAL, "deferred_shade_env: workspace smaller than "
+                                 "dirt_deferred_shade_env_workspace() reports");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ShadeEnvArgs A = {camera_position, camera_per_frame != 0, {coefficients, coeffs_per_frame != 0, 1}};
+    float *partial = want_params ? static_cast<float *>(workspace) : nullptr;
+    with_sh_coeff_count(n_coeffs, [&](auto k) {
+        launch_shade_env_bwd<decltype(k)::value>(positions, colors, normals, material, radiance, occlusion, B, H, W, A,
+                                                 grad_pixels, route, grad_positions, grad_colors, grad_normals,
+                                                 grad_material, grad_radiance, grad_occlusion, partial, stream);
+    });
+    if (want_params)
+        launch_env_reduce(partial, B, H, W, sums, camera_per_frame, coeffs_per_frame,
+                          {grad_camera, grad_coefficients}, stream);
     HIP_TRY(hipGetLastError());
     return DIRT_OK;
 }

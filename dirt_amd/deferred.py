@@ -15,6 +15,11 @@ the dilation does not reach are left out of the shading (exactly 0, `valid` Fals
                            8 lights with a per-pixel, per-light visibility, with gradients to every input
   shade_sh(colors, normals, coefficients, mask=None, normalize=False) -> (pixels, valid): the colours under 1, 4 or 9
                            spherical-harmonic coefficients of the dilated normals, with gradients to all three
+  reflect_view(positions, normals, camera_position) -> (directions, valid): the view vector reflected about the
+                           normal, the direction a specular environment is looked up by; (0, 0, 0) where not valid
+  shade_env(positions, colors, normals, material, coefficients, radiance, camera_position, occlusion=None) ->
+                           (pixels, valid): split-sum image-based lighting of the metallic-roughness material, a
+                           spherical-harmonic irradiance plus a prefiltered radiance times the environment BRDF
   sample_texture(texture, uv, mask=None, wrap="clamp") -> (texels, valid): bilinear texture lookup at a uv G-buffer
   build_mipmaps(texture, levels=None) -> Mipmaps: the box-filtered mip chain, packed
   sample_texture_mip(mipmaps_or_texture, uv, mask=None, wrap="clamp", lod=None, lod_bias=0.0) -> (texels, valid):
@@ -54,6 +59,20 @@ shade_sh lights the colours with an environment instead: 9 (or 4, or 1) RGB sphe
 in the normal and linear in the unknowns (dirt_amd/csrc/shade_sh_kernels.h, C ABI dirt_deferred_shade_sh_*; the
 statement is `_shade_sh_ops`).  One launch forward, two backward as shade_lights', the coefficients' gradient summed in
 a fixed order; it needs no positions, and its normals dilate under their own background or an explicit mask.
+
+reflect_view and shade_env join shade_sh, sample_cubemap_mip and shade_pbr into image-based lighting
+(dirt_amd/csrc/shade_env_kernels.h, C ABI dirt_deferred_reflect_view_* / dirt_deferred_shade_env_*; the statements are
+`_reflect_view_ops`, `_shade_env_ops`):
+
+    directions, _ = reflect_view(positions, normals, camera)
+    radiance, _   = sample_cubemap_mip(chain, directions, lod=material[..., 0] * (len(chain) - 1))
+    pixels, valid = shade_env(positions, colors, normals, material, coefficients, radiance, camera, occlusion=ao)
+
+Both dilate positions and normals by the shade's rule, so that the silhouette ring agrees with `valid`; a pixel that is
+not valid gets the direction (0, 0, 0), which the cube-map lookups leave out.  shade_env uses shade_sh's basis for the
+diffuse half and the analytic fit of the split-sum environment BRDF for the specular half.  One launch forward, two
+backward as shade_lights', every gradient -- G-buffers, material, radiance, occlusion, coefficients, camera --
+bit-identical from run to run; shade_pbr's eligibility and fallback.
 
 sample_texture is the step between the two: UV -> texel, with gradients to the texture and through the uv into the
 geometry (dirt_amd/csrc/texture_kernels.h, C ABI dirt_texture_sample_*; the statement is `_sample_texture_ops`).  Its
@@ -728,19 +747,10 @@ _SH_C = tuple(struct.unpack("f", struct.pack("f", c))[0] for c in (
 _SH_COUNTS = (1, 4, 9)
 
 
-def _shade_sh_ops(colors, normals, coefficients, mask=None, normalize=False):
-    """The framework-op statement of shade_sh, each line one operation: colors, normals [H,W,3] or [B,H,W,3],
-    coefficients [K,3] or [B,K,3], mask (the normals' shape without the channels) or None."""
+def _sh_irradiance_ops(n, coefficients):
+    """E [...,H,W,3] of the vectors n [...,H,W,3] under coefficients [K,3] or [B,K,3]: shade_sh's basis and order of
+    additions, each line one operation."""
     c0, c1, c2, c3, c4 = _SH_C
-    m = torch.isinf(normals).any(-1) if mask is None else mask != 0
-    nrm_d = _dilate_ops(normals, m)
-    valid = torch.isfinite(nrm_d).all(-1, keepdim=True)
-    n = torch.where(valid, nrm_d, 0.0)
-    col = torch.where(valid, colors, 0.0)
-    if normalize:
-        length = torch.linalg.norm(n, dim=-1, keepdim=True)
-        length = length + 1.e-12
-        n = n / length
     x, y, z = n[..., 0:1], n[..., 1:2], n[..., 2:3]
     K = coefficients.shape[-2]
     if coefficients.dim() == 3:
@@ -765,6 +775,22 @@ def _shade_sh_ops(colors, normals, coefficients, mask=None, normalize=False):
     for k in range(1, K):
         term = row(k) * Y[k]
         E = E + term
+    return E
+
+
+def _shade_sh_ops(colors, normals, coefficients, mask=None, normalize=False):
+    """The framework-op statement of shade_sh, each line one operation: colors, normals [H,W,3] or [B,H,W,3],
+    coefficients [K,3] or [B,K,3], mask (the normals' shape without the channels) or None."""
+    m = torch.isinf(normals).any(-1) if mask is None else mask != 0
+    nrm_d = _dilate_ops(normals, m)
+    valid = torch.isfinite(nrm_d).all(-1, keepdim=True)
+    n = torch.where(valid, nrm_d, 0.0)
+    col = torch.where(valid, colors, 0.0)
+    if normalize:
+        length = torch.linalg.norm(n, dim=-1, keepdim=True)
+        length = length + 1.e-12
+        n = n / length
+    E = _sh_irradiance_ops(n, coefficients)
     pixels = col * E
     return torch.where(valid, pixels, 0.0), valid
 
@@ -862,9 +888,299 @@ def shade_sh(colors, normals, coefficients, mask=None, normalize=False):
     return _shade_sh_ops(colors, normals, coefficients, mask, normalize)
 
 
+# ---- reflect_view, shade_env: image-based lighting
+
+def _unit_ops(x):
+    """x / (|x| + 1e-12) over the last dimension (the length's subgradient at 0 is 0)"""
+    length = torch.linalg.norm(x, dim=-1, keepdim=True)
+    length = length + 1.e-12
+    return x / length
+
+
+def _per_frame_camera(camera, like):
+    """camera [3] or [B,3] as a tensor of like's dtype and device that broadcasts against [...,H,W,3]"""
+    camera = torch.as_tensor(camera, dtype=like.dtype, device=like.device)
+    return camera[:, None, None, :] if camera.dim() == 2 else camera
+
+
+def _reflect_view_ops(positions, normals, camera_position):
+    """The framework-op statement of reflect_view, each line one operation: positions, normals [H,W,3] or [B,H,W,3],
+    camera [3] or [B,3]."""
+    pos_s, nrm_s, _, valid = _dilated_gbuffers(positions, positions, normals)
+    camera = _per_frame_camera(camera_position, positions)
+    n = _unit_ops(nrm_s)
+    to_camera = camera - pos_s
+    v = _unit_ops(to_camera)
+    nv = (n * v).sum(-1, keepdim=True)
+    t = 2.0 * nv
+    tn = t * n
+    directions = tn - v
+    return torch.where(valid, directions, 0.0), valid
+
+
+def _shade_env_ops(positions, colors, normals, material, coefficients, radiance, camera_position, occlusion=None):
+    """The framework-op statement of shade_env, each line one operation: G-buffers and radiance [H,W,3] or [B,H,W,3],
+    material [...,2], coefficients [K,3] or [B,K,3], camera [3] or [B,3], occlusion [...,1] or None (ones)."""
+    dev, dt = positions.device, positions.dtype
+    as_t = lambda x: torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
+    pos_s, nrm_s, col, valid = _dilated_gbuffers(positions, colors, normals)
+    mat_s = torch.where(valid, as_t(material), 0.0)
+    rad = torch.where(valid, as_t(radiance), 0.0)
+    occ = None if occlusion is None else torch.where(valid, as_t(occlusion), 0.0)
+    camera = _per_frame_camera(camera_position, positions)
+    n = _unit_ops(nrm_s)
+    to_camera = camera - pos_s
+    v = _unit_ops(to_camera)
+    nv = (n * v).sum(-1, keepdim=True)
+    nv = nv.clamp_min(0.0)
+    r = torch.clamp(mat_s[..., 0:1], _lib.PBR_MIN_ROUGHNESS, 1.0)
+    m = torch.clamp(mat_s[..., 1:2], 0.0, 1.0)
+    E = _sh_irradiance_ops(n, as_t(coefficients))
+    f0 = col - 0.04
+    f0 = f0 * m
+    f0 = 0.04 + f0
+    x = 1.0 - r
+    y = 0.0275 * r
+    y = 0.0425 - y
+    z = 0.572 * r
+    z = 1.04 - z
+    w = 0.022 * r
+    w = w - 0.04
+    e = -9.28 * nv
+    e = torch.exp2(e)
+    q = x * x
+    s = torch.where(q < e, q, e)  # (a select: the gradient goes to the chosen side only)
+    a = s * x
+    a = a + y
+    a104 = 1.04 * a
+    A = z - a104
+    B = a104 + w
+    S = f0 * A
+    S = S + B
+    kd = 1.0 - m
+    kd = kd * col
+    dif = kd * E
+    spec = rad * S
+    pixels = dif + spec
+    if occ is not None:
+        pixels = occ * pixels
+    return torch.where(valid, pixels, 0.0), valid
+
+
+def _valid_outputs(ctx, valid):
+    """the kernels' 0 / 1 bytes as the bool `valid` result, which carries no gradient (as the shade's)"""
+    valid = valid.view(torch.bool)
+    ctx.mark_non_differentiable(valid)
+    ctx.set_materialize_grads(False)
+    return valid
+
+
+class _ReflectViewFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, positions, normals, camera):
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        directions = torch.empty_like(positions)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        route = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        cam_pf = 1 if camera.dim() == 2 else 0
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_deferred_reflect_view_fwd(
+                positions.data_ptr(), normals.data_ptr(), B, H, W, cam_pf, camera.data_ptr(), directions.data_ptr(),
+                valid.data_ptr(), route.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(positions, normals, camera, route)
+        return directions, _valid_outputs(ctx, valid)
+
+    @staticmethod
+    def backward(ctx, grad_directions, _grad_valid):
+        _no_double_backward("reflect_view")
+        if grad_directions is None:
+            return (None,) * 3
+        *saved, route = ctx.saved_tensors
+        positions, normals, camera = saved
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        grad_directions = grad_directions.contiguous()
+        # (NULL for the gradients nobody needs: the kernels then skip them, and without the camera's the partial sums
+        # and the second launch as well)
+        grads = [torch.empty_like(t) if need else None for t, need in zip(saved, ctx.needs_input_grad[:3])]
+        lib = _lib.load()
+        workspace, size = None, _lib._SZ(0)
+        if grads[2] is not None:
+            _lib.check(lib.dirt_deferred_reflect_view_workspace(B, H, W, ctypes.byref(size)))
+            workspace = torch.empty((max(size.value, 4),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.dirt_deferred_reflect_view_bwd(
+                positions.data_ptr(), normals.data_ptr(), B, H, W, 1 if camera.dim() == 2 else 0, camera.data_ptr(),
+                grad_directions.data_ptr(), route.data_ptr(), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]),
+                _ptr(workspace), size.value, _stream(dev)))
+        return tuple(grads)
+
+
+def _env_camera(fn, camera_position, positions):
+    """camera_position as a tensor ([3] or [B,3], checked)"""
+    if not isinstance(camera_position, torch.Tensor):
+        camera_position = torch.as_tensor(camera_position, dtype=positions.dtype, device=positions.device)
+    frames = positions.shape[0] if positions.dim() == 4 else None
+    if tuple(camera_position.shape) not in ((3,), (frames, 3)):
+        raise ValueError("%s: camera_position must be [3] or [B, 3]" % fn)
+    return camera_position
+
+
+def _env_dims_fit(positions):
+    return 1 <= min(positions.shape[-3:-1]) and max(positions.shape[-3:-1]) <= _lib.MAX_DIM
+
+
+def reflect_view(positions, normals, camera_position):
+    """The reflection of the view vector about the normal, per pixel: the direction `sample_cubemap` and
+    `sample_cubemap_mip` look a specular environment up by.
+
+    positions, normals: [H,W,3] or [B,H,W,3] over a -inf background, dilated under the positions' background by
+    `shade`'s rule.  camera_position: [3] or [B,3].  For a valid pixel with dilated position p and dilated normal n_d,
+    u(x) = x / (|x| + 1e-12) (subgradient 0 at 0):
+
+        n = u(n_d)   v = u(camera - p)   R = (2 n . v) n - v
+
+    n . v is not clamped: a back-facing normal reflects to below the surface.  Returns (directions, valid): valid
+    [..., H, W, 1] bool is `shade`'s; an invalid pixel's direction is exactly (0, 0, 0), which both cube-map lookups
+    leave out (their `valid` False, texel 0), so the chain needs no mask.
+
+    On the GPU (float32 tensors on one device) the forward is one fused launch and the backward two, whichever of
+    positions, normals and the camera need gradients; the camera's is summed in a fixed order: bit-identical from run
+    to run."""
+    fn = "reflect_view"
+    positions = torch.as_tensor(positions)
+    normals = torch.as_tensor(normals, dtype=positions.dtype, device=positions.device)
+    if positions.dim() not in (3, 4) or positions.shape[-1] != 3 or normals.shape != positions.shape:
+        raise ValueError("%s: positions, normals must share one shape [H, W, 3] or [B, H, W, 3]" % fn)
+    camera_position = _env_camera(fn, camera_position, positions)
+    if _FUSED_ENABLED and _gpu_f32(positions, normals) and _env_dims_fit(positions):
+        frames = positions.shape[0] if positions.dim() == 4 else None
+        cam = _lights_param(camera_position, positions, ((3,), (frames, 3)))
+        if cam is not None:
+            (pb, added), (nb, _) = _batched(positions), _batched(normals)
+            return _unbatched(_ReflectViewFn.apply(pb, nb, cam), added)
+    return _reflect_view_ops(positions, normals, camera_position)
+
+
+class _ShadeEnvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, positions, colors, normals, material, radiance, occlusion, coefficients, camera):
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        pixels = torch.empty_like(positions)
+        valid = torch.empty((B, H, W, 1), dtype=torch.uint8, device=dev)
+        route = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        ctx.args = (coefficients.shape[-2], 1 if coefficients.dim() == 3 else 0, 1 if camera.dim() == 2 else 0)
+        K, coeffs_pf, cam_pf = ctx.args
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dirt_deferred_shade_env_fwd(
+                positions.data_ptr(), colors.data_ptr(), normals.data_ptr(), material.data_ptr(), radiance.data_ptr(),
+                _ptr(occlusion), B, H, W, K, coeffs_pf, coefficients.data_ptr(), cam_pf, camera.data_ptr(),
+                pixels.data_ptr(), valid.data_ptr(), route.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(positions, colors, normals, material, radiance, occlusion, coefficients, camera, route)
+        return pixels, _valid_outputs(ctx, valid)
+
+    @staticmethod
+    def backward(ctx, grad_pixels, _grad_valid):
+        _no_double_backward("shade_env")
+        if grad_pixels is None:
+            return (None,) * 8
+        *saved, route = ctx.saved_tensors
+        positions, colors, normals, material, radiance, occlusion, coefficients, camera = saved
+        K, coeffs_pf, cam_pf = ctx.args
+        B, H, W, _ = positions.shape
+        dev = positions.device
+        grad_pixels = grad_pixels.contiguous()
+        # (NULL for the gradients nobody needs: the kernels then skip them, and with no parameter among them the
+        # partial sums and the second launch as well)
+        grads = [torch.empty_like(t) if need and t is not None else None
+                 for t, need in zip(saved, ctx.needs_input_grad[:8])]
+        lib = _lib.load()
+        workspace, size = None, _lib._SZ(0)
+        if any(g is not None for g in grads[6:]):
+            _lib.check(lib.dirt_deferred_shade_env_workspace(B, H, W, K, ctypes.byref(size)))
+            workspace = torch.empty((max(size.value, 4),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.dirt_deferred_shade_env_bwd(
+                positions.data_ptr(), colors.data_ptr(), normals.data_ptr(), material.data_ptr(), radiance.data_ptr(),
+                _ptr(occlusion), B, H, W, K, coeffs_pf, coefficients.data_ptr(), cam_pf, camera.data_ptr(),
+                grad_pixels.data_ptr(), route.data_ptr(), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]),
+                _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]), _ptr(grads[6]), _ptr(grads[7]), _ptr(workspace),
+                size.value, _stream(dev)))
+        return tuple(grads)
+
+
+def shade_env(positions, colors, normals, material, coefficients, radiance, camera_position, occlusion=None):
+    """Image-based lighting of a metallic-roughness material by the split-sum approximation: a diffuse irradiance
+    environment (spherical harmonics, as `shade_sh`) plus a prefiltered specular environment (`radiance`, usually
+    `sample_cubemap_mip` at `reflect_view`'s directions and lod = roughness * (levels - 1)) times the analytic fit of
+    the environment BRDF.  `shade_pbr`'s analytic lights add on top.
+
+    positions, colors, normals: the G-buffers, as for `shade_pbr`; colors is the base colour.  material [...,H,W,2]:
+    channel 0 the perceptual roughness, channel 1 the metallic.  coefficients: [K,3] shared by the frames or [B,K,3]
+    one set per frame, K = 1, 4 or 9, in `shade_sh`'s basis, order and constants; the cosine-lobe factors and any
+    1 / pi are the caller's to fold in.  radiance [...,H,W,3].  camera_position: [3] or [B,3].  occlusion: None (ones)
+    or [...,H,W,1], an ambient-occlusion factor on both terms.  colors, material, radiance and occlusion are read at
+    the pixel itself, never dilated, and are not part of `valid`.
+
+    Dilation of positions and normals, `valid` and the returned (pixels, valid) are `shade`'s.  For a valid pixel with
+    dilated position p, dilated normal n_d and colour c, u(x) = x / (|x| + 1e-12):
+
+        n = u(n_d)   v = u(camera - p)   nv = max(n . v, 0)
+        r = clamp(material_0, 0.045, 1)   m = clamp(material_1, 0, 1)
+        E = coefficients_0 Y_0 + coefficients_1 Y_1(n) + ...         (shade_sh's Y_k and order of additions)
+        F0 = 0.04 + (c - 0.04) m
+        x = 1 - r   y = 0.0425 - 0.0275 r   z = 1.04 - 0.572 r   w = 0.022 r - 0.04
+        e = exp2(-9.28 nv)   q = x^2   s = min(q, e), the gradient to the chosen side only
+        a = s x + y          A = z - 1.04 a          B = 1.04 a + w
+        pixels = occlusion (((1 - m) c) E + radiance (F0 A + B))
+
+    B may reach about -0.0024 at r = 1; there is no clamp.  Every clamp takes torch.clamp's derivative, so a roughness
+    below 0.045 receives a zero gradient; max(., 0) passes the gradient where its argument is >= 0.
+
+    On the GPU (float32 tensors on one device) the forward is one fused launch and the backward two, whichever inputs
+    need gradients: the G-buffers, the material, the radiance, the occlusion, the coefficients and the camera.  A
+    parameter's gradient is the sum of its per-pixel terms in a fixed order: bit-identical from run to run."""
+    fn = "shade_env"
+    positions, colors, normals = _gbuffers(fn, positions, colors, normals)
+    dev, dt = positions.device, positions.dtype
+    as_t = lambda x: x if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
+    material, radiance, coefficients = as_t(material), as_t(radiance), as_t(coefficients)
+    if material.shape != positions.shape[:-1] + (2,):
+        raise ValueError("%s: material of shape %s for positions of shape %s; it must be [..., H, W, 2]"
+                         % (fn, tuple(material.shape), tuple(positions.shape)))
+    if radiance.shape != positions.shape:
+        raise ValueError("%s: radiance of shape %s for positions of shape %s; it must be [..., H, W, 3]"
+                         % (fn, tuple(radiance.shape), tuple(positions.shape)))
+    if occlusion is not None:
+        occlusion = as_t(occlusion)
+        if occlusion.shape != positions.shape[:-1] + (1,):
+            raise ValueError("%s: occlusion of shape %s for positions of shape %s; it must be [..., H, W, 1]"
+                             % (fn, tuple(occlusion.shape), tuple(positions.shape)))
+    if coefficients.dim() not in (2, 3) or coefficients.shape[-1] != 3:
+        raise ValueError("%s: coefficients must be [K, 3] or [B, K, 3]" % fn)
+    K = coefficients.shape[-2]
+    if K not in _SH_COUNTS:
+        raise ValueError("%s: %d coefficients; K must be 1, 4 or 9 (bands 0, 0-1, 0-2)" % (fn, K))
+    frames = positions.shape[0] if positions.dim() == 4 else None
+    if coefficients.dim() == 3 and coefficients.shape[0] != frames:
+        raise ValueError("%s: per-frame coefficients need one set per frame of a [B, H, W, 3] batch" % fn)
+    camera_position = _env_camera(fn, camera_position, positions)
+    if _FUSED_ENABLED and _gpu_f32(positions, colors, normals, material, radiance) and _env_dims_fit(positions) and \
+            (occlusion is None or _gpu_f32(positions, occlusion)):
+        coef = _lights_param(coefficients, positions, ((K, 3), (frames, K, 3)))
+        cam = _lights_param(camera_position, positions, ((3,), (frames, 3)))
+        if coef is not None and cam is not None:
+            ops, added = zip(*(_batched(x) for x in (positions, colors, normals, material, radiance)))
+            occ = None if occlusion is None else _batched(occlusion)[0]
+            return _unbatched(_ShadeEnvFn.apply(*ops, occ, coef, cam), added[0])
+    return _shade_env_ops(positions, colors, normals, material, coefficients, radiance, camera_position, occlusion)
+
+
 # ---- texture sampling
 
-_WRAPS = {"clamp": _lib.TEXTURE_CLAMP, "repeat": _lib.TEXTURE_REPEAT}
+_WRAPS ={"clamp": _lib.TEXTURE_CLAMP, "repeat": _lib.TEXTURE_REPEAT}
 
 
 def _texture_axis(u, T, wrap):

@@ -84,7 +84,9 @@ extern "C" {
  * dirt_deferred_shade_sh_fwd, dirt_deferred_shade_sh_bwd, dirt_texture_sample_cube_fwd,
  * dirt_texture_sample_cube_bwd, dirt_texture_sample_cube_mip_fwd, dirt_texture_sample_cube_mip_bwd,
  * dirt_shadow_sample_workspace, dirt_shadow_sample_fwd, dirt_shadow_sample_bwd, dirt_deferred_shade_pbr_workspace,
- * dirt_deferred_shade_pbr_fwd, dirt_deferred_shade_pbr_bwd) */
+ * dirt_deferred_shade_pbr_fwd, dirt_deferred_shade_pbr_bwd, dirt_deferred_reflect_view_workspace,
+ * dirt_deferred_reflect_view_fwd, dirt_deferred_reflect_view_bwd, dirt_deferred_shade_env_workspace,
+ * dirt_deferred_shade_env_fwd, dirt_deferred_shade_env_bwd) */
 int dirt_abi_version(void);
 
 /* Byte sizes of the caller-provided buffers for one call.
@@ -446,6 +448,62 @@ int dirt_deferred_shade_sh_bwd(const float *colors, const float *normals, int B,
                                const float *grad_pixels, const uint32_t *route, float *grad_colors,
                                float *grad_normals, float *grad_coefficients, void *workspace,
                                size_t workspace_bytes, void *stream);
+
+/* Image-based lighting: the two steps between deferred_shade_sh, texture_sample_cube_mip and deferred_shade_pbr.
+ * Dilation of positions and normals under the positions' background, valid and the route word are deferred_shade's;
+ * camera_position is a DEVICE array [3], or [B,3] with camera_per_frame != 0.  u(x) = x / (|x| + 1e-12).
+ *
+ * deferred_reflect_view: the reflection of the view vector about the normal, directions [B,H,W,3].  For a valid pixel
+ * with dilated position p and dilated normal n_d, float32, every step one IEEE operation:
+ *   n = u(n_d)  v = u(camera - p)  nvr = n . v (not clamped)  t = 2 nvr  R = t n - v
+ * and exactly (0, 0, 0) at an invalid pixel, a direction both cube-map lookups leave out.
+ *
+ * deferred_shade_env: the split-sum combination of a diffuse irradiance environment (coefficients: deferred_shade_sh's
+ * basis, order and constants; [n_coeffs,3], or [B,n_coeffs,3] with coeffs_per_frame != 0; n_coeffs 1, 4 or 9) and a
+ * prefiltered specular one (radiance [B,H,W,3]).  colors, material [B,H,W,2] (perceptual roughness, metallic), radiance
+ * and occlusion [B,H,W] (NULL = ones) are read at the pixel itself.  For a valid pixel with colour c:
+ *   n = u(n_d)  v = u(camera - p)  nv = max(n . v, 0)
+ *   r = clamp(material_0, DIRT_PBR_MIN_ROUGHNESS, 1)  m = clamp(material_1, 0, 1)
+ *   E = coefficients_0 Y_0 + coefficients_1 Y_1(n) + ...   (deferred_shade_sh's order of additions)
+ *   F0 = 0.04 + (c - 0.04) m
+ *   x = 1 - r  y = 0.0425 - 0.0275 r  z = 1.04 - 0.572 r  w = 0.022 r - 0.04
+ *   e = exp2(-9.28 nv)  q = x x  s = q < e ? q : e  a = s x + y  A = z - 1.04 a  B = 1.04 a + w
+ *   S = F0 A + B  dif = ((1 - m) c) E  spec = radiance S  pixels = occlusion (dif + spec)
+ * and 0 at an invalid pixel.  The cosine-lobe factors and any 1 / pi are the caller's to fold into the coefficients.
+ *
+ * Backward: grad_positions / grad_normals are gathers through the dilation route as deferred_shade_bwd's; grad_colors,
+ * grad_material, grad_radiance, grad_occlusion receive their own pixel's terms (every clamp with torch.clamp's
+ * derivative, max(., 0) passing where its argument is >= 0, the select passing to its chosen side only);
+ * grad_coefficients and grad_camera (shaped as their parameters) receive the sums of the per-pixel terms over the
+ * valid pixels of a frame (per-frame parameters) or of all frames (shared ones).  Each may be NULL; each requested one
+ * is fully overwritten.  With a parameter gradient requested, `workspace` must hold dirt_deferred_*_workspace() bytes
+ * = B * ceil(H W / 256) * P * 4 (it needs no clearing), P = 3 (reflect_view: the camera) or 3 + 3 n_coeffs (shade_env:
+ * the camera, then the coefficients in index order): the first kernel stores per-chunk partial sums there -- one
+ * workgroup per 256 contiguous pixels of a frame, wave butterflies, then the four waves in order -- and a second kernel
+ * on the same stream adds the chunks of a frame and then the frames in fixed orders.  No float atomics: every gradient
+ * is bit-identical from run to run.  B == 0, or nothing requested, is DIRT_OK without a launch. */
+int dirt_deferred_reflect_view_workspace(int B, int H, int W, size_t *bytes);
+int dirt_deferred_reflect_view_fwd(const float *positions, const float *normals, int B, int H, int W,
+                                   int camera_per_frame, const float *camera_position, float *directions,
+                                   uint8_t *valid, uint32_t *route, void *stream);
+int dirt_deferred_reflect_view_bwd(const float *positions, const float *normals, int B, int H, int W,
+                                   int camera_per_frame, const float *camera_position, const float *grad_directions,
+                                   const uint32_t *route, float *grad_positions, float *grad_normals,
+                                   float *grad_camera, void *workspace, size_t workspace_bytes, void *stream);
+int dirt_deferred_shade_env_workspace(int B, int H, int W, int n_coeffs, size_t *bytes);
+int dirt_deferred_shade_env_fwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *radiance, const float *occlusion, int B, int H,
+                                int W, int n_coeffs, int coeffs_per_frame, const float *coefficients,
+                                int camera_per_frame, const float *camera_position, float *pixels, uint8_t *valid,
+                                uint32_t *route, void *stream);
+int dirt_deferred_shade_env_bwd(const float *positions, const float *colors, const float *normals,
+                                const float *material, const float *radiance, const float *occlusion, int B, int H,
+                                int W, int n_coeffs, int coeffs_per_frame, const float *coefficients,
+                                int camera_per_frame, const float *camera_position, const float *grad_pixels,
+                                const uint32_t *route, float *grad_positions, float *grad_colors, float *grad_normals,
+                                float *grad_material, float *grad_radiance, float *grad_occlusion,
+                                float *grad_coefficients, float *grad_camera, void *workspace, size_t workspace_bytes,
+                                void *stream);
 
 /* Deferred texturing: bilinear sampling of a texture at a uv G-buffer, and its gradients.
  * texture [texture_frames,Th,Tw,C] (texture_frames = 1: shared by the B frames, = B: one per frame), uv [B,H,W,2],
